@@ -18,8 +18,8 @@ A *step* is one federated round with the reference's semantics
      split over the clients (they all hold the same averaged model; per-round
      (loss, correct, count) summed over clients in one collective -- the same
      numbers, 1/N of the eval work) and reports it as
-     ``rounds_per_sec_eval_split``; ``--eval-split`` makes that the headline
-     ``value`` instead (labelled in ``config.eval_split``)
+     ``rounds_per_sec_eval_split`` (``--full`` only); ``--eval-split`` makes that
+     the headline ``value`` instead (labelled in ``config.eval_split``)
   4. the global model is persisted as Primary/optimizedModel.pth (rank 0) and
      every client checkpoint as checkpoint/<client>.pth ({'net','acc','epoch'}),
      by the native C++ writer (csrc/runtime/ckpt_writer.cpp: async device->pinned
@@ -30,7 +30,14 @@ A *step* is one federated round with the reference's semantics
 Total work per round is fixed (50k samples split over N clients) -> strong
 scaling.  ``value`` is the whole-job training throughput (samples/s summed over
 clients = 50,000 x rounds/s); rounds/s and samples/s/client are reported too.
-Data: synthetic CIFAR-shaped uint8 images, random-init weights.
+Data: synthetic CIFAR-shaped uint8 images, random-init weights (seeded: the same
+arguments give the same inputs in every run).
+
+A plain run sets up, warms up, times ``--steps`` rounds and prints the result
+line.  ``--full`` adds what the headline figure does not need: the split-eval
+loop above and, at one client, the end-of-run consistency guard (at N>1 the guard
+always runs -- a run whose clients diverged did not measure FedAvg).
+``--dump-outputs DIR`` writes what the last timed round computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -140,6 +147,39 @@ def make_transport(args, trainer, rank: int, world: int, rehearse: bool, device)
     return peer, info
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def collect_outputs(trainer, eval_stats) -> dict:
+    """Host copies of what a caller of the round holds after it, by name: the model's flat fp32 state
+    (the averaged global model), its integer buffers (every BatchNorm counter, as float64), and the
+    (loss_sum, correct, count) of the local epoch and of the evaluation.  A state over the size limit
+    is cut to a fixed seeded sample."""
+    import numpy as np
+
+    w = trainer.float_state().detach().float().cpu().numpy().reshape(-1)
+    room = (DUMP_MAX_BYTES - (1 << 20)) // 4            # 1 MiB left for the small arrays and the headers
+    if w.size > room:
+        w = w[np.sort(np.random.default_rng(0).choice(w.size, room, replace=False))]
+    out = {"float_state": np.ascontiguousarray(w, dtype=np.float32)}
+    ints = [t.detach().reshape(-1) for t in trainer.int_state()]
+    if ints:
+        out["int_state"] = torch.cat(ints).double().cpu().numpy()
+    for name, st in (("train_stats", trainer.train_stats()), ("eval_stats", eval_stats)):
+        if st is not None:
+            out[name] = np.asarray([st.loss_sum, st.correct, st.count], dtype=np.float64)
+    return out
+
+
+def dump_outputs(out_dir: Path, arrays: dict) -> None:
+    """``--dump-outputs``: :func:`collect_outputs` as ``out_dir/<name>.npy``."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gpus", type=int, default=1)
@@ -164,8 +204,14 @@ def main() -> int:
     ap.add_argument("--eval-split", action="store_true",
                     help="headline loop with the 10k test set split over the clients and the accumulators summed "
                          "(same numbers, 1/N of the eval work); labelled in config.eval_split")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: at N>1 the second timed loop that "
+                         "measures the split-eval round, at one client the end-of-run consistency guard")
     ap.add_argument("--no-split-compare", action="store_true",
-                    help="N>1: skip the second timed loop that measures the split-eval round")
+                    help="--full at N>1: skip the second timed loop that measures the split-eval round")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed rounds write what the last one computed (model state, train and eval "
+                         "accumulators) as DIR/<name>.npy")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--ckpt-dir", default=None)
     # 2 slots: the writer takes 0.22 ms per LeNet round (profiles/r6_lenet/ckpt_write_probe.jsonl), so 2 keep it off
@@ -253,8 +299,10 @@ def main() -> int:
     split_eval = shard_world > 1 and args.eval_split
     if split_eval:
         trainer.set_test_data(eval_shard(data.test, rank, shard_world))
-    # N>1 with full per-client eval: a second timed loop measures the split-eval round (reported, not headline)
-    compare_split = shard_world > 1 and not split_eval and not args.no_split_compare and not args.no_eval
+    # --full at N>1 with full per-client eval: a second timed loop measures the split-eval round (reported,
+    # not headline)
+    compare_split = (args.full and shard_world > 1 and not split_eval and not args.no_split_compare
+                     and not args.no_eval)
     hist = EvalHistory(trainer, args.warmup + args.steps + (args.steps + 1 if compare_split else 0))
     if args.trace:
         ys = trainer.train_set.y.long().cpu()
@@ -335,6 +383,14 @@ def main() -> int:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     T = float(elapsed.item())
     full_eval_stats = trainer.eval_stats() if not args.no_eval and not split_eval else None
+    if args.no_eval:
+        ev_stats = None
+    elif rounds_eval is not None:
+        ev_stats = rounds_eval[-1]
+    else:
+        ev_stats = full_eval_stats
+    # --dump-outputs: host copies now (the split-eval loop below trains on), the files after the last collective
+    outputs = collect_outputs(trainer, ev_stats) if args.dump_outputs and rank == 0 else None
     T_split = None
     if compare_split:
         # the same rounds with the test set split over the clients (after the headline's timed region)
@@ -354,19 +410,16 @@ def main() -> int:
         T_split = float(el2.item())
 
     # end-of-run guard (outside the timed region): no peer barrier timed out on any rank and every
-    # client holds the bit-identical global model -- else the throughput above is not a FedAvg run
-    from fedmi.parallel.consistency import check_consistency
+    # client holds the bit-identical global model -- else the throughput above is not a FedAvg run.
+    # One client has no peer to diverge from: there the guard runs under --full only
+    consistency = None
+    if world > 1 or args.full:
+        from fedmi.parallel.consistency import check_consistency
 
-    consistency = check_consistency(trainer, transport=transport, device=device, compressor=agg.compressor)
+        consistency = check_consistency(trainer, transport=transport, device=device, compressor=agg.compressor)
     breakdown = dict(_breakdown(marks, PHASES, t0, t1, args.steps), tail=tail) if args.breakdown else None
 
     tr_stats = trainer.train_stats()
-    if args.no_eval:
-        ev_stats = None
-    elif rounds_eval is not None:
-        ev_stats = rounds_eval[-1]
-    else:
-        ev_stats = full_eval_stats
     rounds_per_s = args.steps / T
     value = rounds_per_s * N_TRAIN / (args.project_world or 1)
     base_r = _baseline_rounds(args.model, world)
@@ -415,7 +468,7 @@ def main() -> int:
         "checkpoint": {"writer": writer.backend, "files_written": writer.written,
                        "rounds_coalesced": writer.coalesced},
         **({"transport_select": select} if select else {}),
-        "consistency": consistency,
+        **({"consistency": consistency} if consistency else {}),
         **({"native_backend": {"aten_fallbacks": sum(trainer.mode.fallbacks.values()),
                                "fallback_ops": dict(trainer.mode.fallbacks),
                                "native_ops": sum(trainer.mode.native_ops.values())}}
@@ -430,7 +483,7 @@ def main() -> int:
     if transport is not None:
         transport.close()          # store barrier first: no rank unmaps memory a peer's kernel may still read
     rc = 0
-    if not consistency["ok"]:
+    if consistency and not consistency["ok"]:
         # no throughput line: a run whose clients diverged did not measure FedAvg
         print(f"[bench] rank {rank}: CONSISTENCY CHECK FAILED {json.dumps(consistency)}", file=sys.stderr, flush=True)
         out["value"] = None
@@ -443,6 +496,8 @@ def main() -> int:
             Path(args.json_out).write_text(line + "\n")
     if world > 1:
         dist.destroy_process_group()
+    if outputs is not None:
+        dump_outputs(Path(args.dump_outputs), outputs)   # last: a failure here leaves no peer inside a collective
     return rc
 
 

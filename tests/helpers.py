@@ -19,6 +19,60 @@ def free_port() -> int:
         return s.getsockname()[1]
 
 
+def state_layout(state_dict) -> list:
+    """[key, shape, dtype] of every entry, sorted by key (two models with the same entries give the same list)."""
+    return sorted([k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in state_dict.items())
+
+
+def pack_layout(layout) -> str:
+    """A :func:`state_layout` as one short string (zlib + base64 of its JSON: the zoo's layouts are 340 KB as
+    text, 34 KB packed); :func:`unpack_layout` gives the list back."""
+    import base64
+    import json
+    import zlib
+
+    return base64.b64encode(zlib.compress(json.dumps(layout, separators=(",", ":")).encode(), 9)).decode()
+
+
+def unpack_layout(packed: str) -> list:
+    import base64
+    import json
+    import zlib
+
+    return json.loads(zlib.decompress(base64.b64decode(packed)))
+
+
+def seeded_state(layout, seed: int = 0) -> "dict[str, torch.Tensor]":
+    """A state dict for ``layout`` (:func:`state_layout`) drawn from one seeded CPU generator, scaled so
+    that a deep network stays finite in eval mode: conv / linear weights with std 1/sqrt(fan_in), 1-d weights
+    (norm scales) in [0.5, 1], running variances in [0.5, 1.5], other float entries 0.1 * N(0, 1), integer
+    entries zero.  tests/golden/model_zoo.json holds the reference models' outputs for these weights
+    (tools/record_reference_golden.py)."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    sd = {}
+    for key, shape, dtype in layout:
+        dt = getattr(torch, dtype)
+        if not dt.is_floating_point:
+            sd[key] = torch.zeros(shape, dtype=dt)
+        elif key.endswith("running_var"):
+            sd[key] = 0.5 + torch.rand(shape, generator=g)
+        elif key.endswith("weight") and len(shape) >= 2:
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            sd[key] = torch.randn(shape, generator=g) / fan_in ** 0.5
+        elif key.endswith("weight"):
+            sd[key] = 0.5 + 0.5 * torch.rand(shape, generator=g)
+        else:
+            sd[key] = 0.1 * torch.randn(shape, generator=g)
+    return sd
+
+
+def seeded_input(seed: int = 1) -> torch.Tensor:
+    """The float64 2x3x32x32 input that goes with :func:`seeded_state`."""
+    return torch.randn(2, 3, 32, 32, generator=torch.Generator(device="cpu").manual_seed(seed)).double()
+
+
 def small_trainer(model="mlp", n_train=512, n_test=256, seed=0, lr=0.05):
     from fedmi.engine import build_trainer
     from fedmi.engine.base import TrainerConfig

@@ -21,7 +21,7 @@ def _run(tmp_path, *extra, world=2):
     env = dict(os.environ, FEDMI_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "bench.py"),
-           "--gpus", str(world), "--steps", "3", "--warmup", "1", "--allreduce", "oneshot",
+           "--gpus", str(world), "--steps", "3", "--warmup", "1", "--allreduce", "oneshot", "--full",
            "--ckpt-dir", str(tmp_path / "ck"), "--json-out", str(out), *extra]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=100)
     js = json.loads(out.read_text()) if out.exists() else None

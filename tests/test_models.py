@@ -1,16 +1,19 @@
 """Model zoo: every reference factory exists, forwards 3x32x32 -> 10 logits, and
 has EXACTLY the reference state-dict keys and shapes (checkpoint interchange
-with reference peers).  The reference model sources are imported read-only
-from /root/reference/src/models when present."""
-import importlib.util
+with reference peers).  What the reference models are is recorded in
+tests/golden/model_zoo.json (tools/record_reference_golden.py): each factory's
+state-dict layout (packed, tests/helpers.py) and its float64 logits for seeded weights
+and a seeded input."""
+import json
 from pathlib import Path
 
 import pytest
 import torch
 
 from fedmi.models import build_model, list_models
+from tests.helpers import seeded_input, seeded_state, state_layout, unpack_layout
 
-REF = Path("/root/reference/src/models")
+GOLDEN = Path(__file__).resolve().parent / "golden" / "model_zoo.json"
 
 # (our registry name, reference file, reference factory expression)
 CASES = [
@@ -40,31 +43,28 @@ PARAMS = {"LeNet": 62006, "VGG11": 9.23e6, "VGG19": 20.04e6, "ResNet18": 11.17e6
           "DLA": 16.29e6, "SimpleDLA": 15.14e6}
 
 
-def _ref_model(fname, expr):
-    if not (REF / f"{fname}.py").exists():
-        pytest.skip("reference model sources not mounted")
-    spec = importlib.util.spec_from_file_location(f"_ref_{fname}", REF / f"{fname}.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return eval(expr, vars(mod))  # noqa: S307  (reference factory call, e.g. "ResNet18()")
+@pytest.fixture(scope="module")
+def golden():
+    return json.loads(GOLDEN.read_text())
 
 
 @pytest.mark.parametrize("name,fname,expr", CASES, ids=[c[0] for c in CASES])
-def test_state_dict_matches_reference(name, fname, expr):
+def test_state_dict_matches_reference(golden, name, fname, expr):
     torch.manual_seed(0)
     ours = build_model(name)
-    ref = _ref_model(fname, expr)
-    so, sr = ours.state_dict(), ref.state_dict()
-    assert list(so) == list(sr) or set(so) == set(sr), set(so) ^ set(sr)
+    layout = state_layout(ours.state_dict())          # sorted [key, shape, dtype]
+    so = {k: (shape, dtype) for k, shape, dtype in layout}
+    sr = {k: (shape, dtype) for k, shape, dtype in unpack_layout(golden[name]["layout"])}   # the reference model's
+    assert set(so) == set(sr), set(so) ^ set(sr)
     for k in sr:
-        assert so[k].shape == sr[k].shape, k
-    # weights are interchangeable: load the reference's and reproduce its outputs
-    ours.load_state_dict(sr)
-    ours.eval()
-    ref.eval()
-    x = torch.randn(2, 3, 32, 32)
+        assert so[k] == sr[k], k
+    # weights are interchangeable: load the ones the reference model was given and reproduce its outputs
+    # (float64 on both sides, so the recorded logits do not depend on the CPU they were computed on)
+    ours.load_state_dict(seeded_state(layout))
+    ours.double().eval()
     with torch.no_grad():
-        assert torch.allclose(ours(x), ref(x), atol=1e-4, rtol=1e-4)
+        y = ours(seeded_input())
+    assert torch.allclose(y, torch.tensor(golden[name]["logits"], dtype=torch.float64), atol=1e-4, rtol=1e-4)
 
 
 @pytest.mark.parametrize("name", sorted(PARAMS))

@@ -128,8 +128,8 @@ case "$run" in
     o=gpurun_out/r6_ao
     mkdir -p $o
     bash tools/gpu_steps.sh r6_ao \
-      reh2 300 "FEDMI_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29621 bench.py --gpus 2 --steps 5 --warmup 2 --json-out $o/reh2.json" \
-      reh4 300 "FEDMI_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29622 bench.py --gpus 4 --steps 5 --warmup 2 --json-out $o/reh4.json"
+      reh2 300 "FEDMI_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29621 bench.py --gpus 2 --steps 5 --warmup 2 --full --json-out $o/reh2.json" \
+      reh4 300 "FEDMI_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29622 bench.py --gpus 4 --steps 5 --warmup 2 --full --json-out $o/reh4.json"
     ;;
   ap)
     # round 6: 1x1 WGRAD on conv_wgrad_halo<1, 1> -- kernel tests, engine bit-identity tests, A/B (FEDMI_WGRAD_1X1=0)
@@ -215,8 +215,8 @@ case "$run" in
     bash tools/gpu_steps.sh r6_d \
       int8test 300 "python -u -m pytest tests/test_peer_comm_gpu.py -k 'int8 or abort' -x -v --timeout 240 --timeout-method thread -p no:cacheprovider" \
       peerbench 300 "python tools/bench_peer.py --world 2 4 --iters 200 --no-gate --out $o/peer_nogate.jsonl" \
-      reh2 300 "FEDMI_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 5 --warmup 2 --json-out $o/reh2.json" \
-      reh4y 300 "FEDMI_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 4 --steps 5 --warmup 2 --compress Y --json-out $o/reh4y.json" \
+      reh2 300 "FEDMI_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 5 --warmup 2 --full --json-out $o/reh2.json" \
+      reh4y 300 "FEDMI_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 4 --steps 5 --warmup 2 --full --compress Y --json-out $o/reh4y.json" \
       googprof 300 "MODELS=googlenet bash tools/gpu_prof_models.sh r6_d/prof"
     ;;
   e)
