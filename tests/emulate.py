@@ -6,8 +6,9 @@ activations, fp32 stats, outputs written in place) but computes with plain
 torch ops, so the native engines' *wiring* — which buffer feeds which launch,
 residual fan-in, BN branch pairing, running-stat updates — can be verified on
 a CPU-only host.  :func:`emulated` swaps them in for the duration of a
-``with`` block.  Never used on a GPU run: the native paths fail loudly when
-the extension is missing instead of falling back here.
+``with`` block.  Never a fallback on a GPU run: the native paths fail loudly
+when the extension is missing.  On the GPU the functions only serve as the
+per-launch reference of tests/shadow.py, next to the native call.
 """
 from __future__ import annotations
 
@@ -89,14 +90,18 @@ def _w_from_img(wr: torch.Tensor, Cw: Optional[int]) -> torch.Tensor:
     return w if Cw is None else w[:, :Cw]
 
 
+def stats_sums(y_nhwc, shift=None):
+    """[2, C] fp64 channel sums (sum, sum of squares) of (y - shift), as the conv epilogues accumulate them."""
+    v = y_nhwc.double().reshape(-1, y_nhwc.shape[-1])
+    if shift is not None:
+        v = v - shift.double()
+    return torch.stack((v.sum(0), (v * v).sum(0)))
+
+
 def _stats_add(stats, y_bf16_nhwc, shift=None):
     if stats is not None:
-        v = y_bf16_nhwc.float().reshape(-1, y_bf16_nhwc.shape[-1])
-        if shift is not None:
-            v = v - shift
-        rep0 = stats.view(conv.STAT_REP, 2, -1)[0]     # replica 0 (the native kernels spread over all)
-        rep0[0] += v.sum(0)
-        rep0[1] += (v * v).sum(0)
+        # fp64 like the native accumulators (fp64 atomics): the reference is not the less precise side
+        stats.view(conv.STAT_REP, 2, -1)[0] += stats_sums(y_bf16_nhwc, shift)   # replica 0 (native: spread over all)
 
 
 @torch.no_grad()
@@ -330,15 +335,18 @@ def bn_bwd(dya, za, a, dgamma_a, dbeta_a, dza, red, dyb=None, y=None, zb=None, b
     if y is not None:
         g = torch.where(y.float().reshape(M, C) > 0, g, torch.zeros_like(g))
     elif mask_bn is not None:
-        g = torch.where(za.float().reshape(M, C) * mask_bn[0] + mask_bn[1] > 0, g, torch.zeros_like(g))
+        # in fp64 the product and the sum are exact for bf16 / fp32 z: the sign is that of the kernels' fused
+        # multiply-add (an unfused fp32 evaluation flips elements at rounding distance from zero)
+        g = torch.where(za.double().reshape(M, C) * mask_bn[0].double() + mask_bn[1].double() > 0, g,
+                        torch.zeros_like(g))
     if gout is not None:
         gout.copy_(g.reshape(gout.shape).to(gout.dtype))
-    sg = g.sum(0)
+    sg = g.double().sum(0).float()     # channel sums in fp64, like the native fp64 accumulators
     for z, p, dg, db, dz in ((za, a, dgamma_a, dbeta_a, dza), (zb, b, dgamma_b, dbeta_b, dzb)):
         if z is None:
             continue
         xhat = (z.float().reshape(M, C) - p.smean) * p.sinv
-        sgx = (g * xhat).sum(0)
+        sgx = (g.double() * xhat.double()).sum(0).float()
         dg.copy_(sgx)
         db.copy_(sg)
         if p.shift is not None:

@@ -908,3 +908,65 @@ def test_conv_fwd_tap_gen_sweep(gpu_device):
         stats = conv.stats_total(rep)
         yb = y.float()
         assert torch.allclose(stats[0], yb.sum((0, 1, 2)), rtol=1e-3, atol=5e-2), shape
+
+
+def test_bn_bwd_z_mask_at_rounding_distance_is_the_fused_sign(gpu_device):
+    """The z-derived ReLU mask (``mask_bn`` / ``bn_sums`` msc) is the sign of the FUSED z * sc + sh, in the DGRAD
+    epilogue that sums and in the bn_bwd pass that applies -- reduced from the engine call the op-by-op shadow
+    flagged (MobileNet, batch 80: 1x1 512 -> 512 at 4x4, bn_bwd chained + presummed + mask_bn), where one element
+    at rounding distance from zero moved dbeta past its tolerance against an unfused fp32 reference.  Here a
+    quarter of the rows sit AT the threshold of their channel: sh = -fp32(z0 * sc), so the unfused value is
+    exactly 0 (masked) and the fused one is the product's rounding residual, of either sign."""
+    dev = gpu_device
+    N, H, W, C = 80, 4, 4, 512
+    M = N * H * W
+    g = torch.Generator(device="cpu").manual_seed(21)
+    z = torch.randn(M, C, generator=g).to(dev).bfloat16()
+    sc = (torch.rand(C, generator=g) + 0.5).to(dev)
+    z[::4] = z[0]
+    sh = -(z[0].float() * sc)
+    msc = torch.stack([sc, sh]).contiguous()
+    exact = z.double() * sc.double() + sh.double()      # exact in fp64: 8-bit x 24-bit product, then one sum
+    mask = exact > 0
+    unfused = (z.float() * sc) + sh > 0
+    assert float((mask != unfused).float().mean()) > 0.05     # the two evaluations really differ here
+    gamma = (torch.rand(C, generator=g) + 0.5).to(dev)
+    mean, inv = (torch.randn(C, generator=g) * 0.1).to(dev), (torch.rand(C, generator=g) + 0.5).to(dev)
+    w = (torch.randn(C, C, 1, 1, generator=g) / C ** 0.5).to(dev)
+    dyn = torch.randn(N, H, W, C, generator=g).to(dev).bfloat16()
+    wpk = conv.pack_weight(w)
+    wd = torch.empty(conv.dgrad_image_numel(w.shape, C), dtype=torch.bfloat16, device=dev)
+    conv.dgrad_pack_weights([(w, wd, 1, 0, C)])
+    shp = ((N, H, W, C), C, 1, 1, 1, 0, C)
+    assert conv.dgrad_fusable(*shp)
+    wsp = torch.empty(max(conv.fd_ws_floats(*shp), 1), device=dev)
+    reps = cnn.bn_bwd_chain_floats(C) // (3 * C)
+    rep = torch.zeros(reps, 3, C, dtype=torch.float64, device=dev)
+    z4 = z.view(N, H, W, C)
+    dx = conv.conv2d_dgrad(dyn, wpk, (N, H, W, C), 1, 0, ws=wsp, wd=wd,
+                           bn_sums=dict(rep=rep.view(-1), reps=reps, z=z4, y=None, mean=mean, inv=inv, msc=msc))
+    torch.cuda.synchronize()
+    gm = torch.where(mask, dx.double().reshape(M, C), torch.zeros(M, C, dtype=torch.float64, device=dev))
+    xhat = (z.double() - mean.double()) * inv.double()
+    s0, s1 = gm.sum(0), (gm * xhat).sum(0)
+    scale = gm.abs().sum(0) + 1.0
+    got = rep.sum(0)
+    assert float(((got[0] - s0).abs() / scale).max()) < 1e-5          # the epilogue's sums (as its own test bounds them)
+    assert float(((got[1] - s1).abs() / (scale * 4)).max()) < 1e-5
+    a = cnn.bn_desc(gamma=gamma, smean=mean, sinv=inv)
+    dg, db = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    dz = torch.empty(M, C, dtype=torch.bfloat16, device=dev)
+    red = torch.zeros(3, C, dtype=torch.float64, device=dev)
+    cnn.bn_bwd(dx.view(M, C), z, a, dg, db, dz, red, ws=rep.view(-1), chained=True, mask_bn=msc, presummed=True)
+    torch.cuda.synchronize()
+    ref = (gamma * inv).double() * (gm - s0 / M - xhat * s1 / M)
+    assert float(((db.double() - s0).abs() / scale).max()) < 1e-5
+    assert float(((dg.double() - s1).abs() / (scale * 4)).max()) < 1e-5
+    assert _rel(dz.float(), ref.float()) < 1e-2
+    # and the stand-alone reduce + apply pair takes the same mask
+    dg2, db2 = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    dz2 = torch.empty(M, C, dtype=torch.bfloat16, device=dev)
+    cnn.bn_bwd(dx.view(M, C), z, a, dg2, db2, dz2, torch.zeros(3, C, dtype=torch.float64, device=dev), mask_bn=msc)
+    torch.cuda.synchronize()
+    assert float(((db2.double() - s0).abs() / scale).max()) < 1e-5
+    assert _rel(dz2.float(), ref.float()) < 1e-2
