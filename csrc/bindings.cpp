@@ -26,6 +26,7 @@ void read_stamps(unsigned long long*, bool);
 void set_ks1_diag(int);
 void launch_lenet_pack(hipStream_t, const float*, bf16*);
 void launch_sgd_flat(hipStream_t, float*, const float*, float*, long, float, float, float, float, int, int);
+void launch_server_opt(hipStream_t, float*, float*, float*, float*, long, long, int, float, float, float, float);
 void launch_ef_delta(hipStream_t, const float*, const float*, const float*, float*, long);
 size_t topk_state_bytes();
 size_t topk_overflow_offset();
@@ -153,6 +154,20 @@ static void fedmi_bind(py::module_& m) {
                     first ? 1 : 0);
     check_last("sgd_flat");
   });
+  // server-side optimizer step on the aggregated state (kind: 0 fedavgm, 1 fedadagrad, 2 fedyogi, 3 fedadam);
+  // v may be 0 for fedavgm
+  m.def("server_opt", [](uintptr_t st, uintptr_t x, uintptr_t anchor, uintptr_t mom, uintptr_t v, long n, long n_opt,
+                         int kind, float lr, float beta1, float beta2, float tau) {
+    if (kind < 0 || kind > 3) throw std::invalid_argument("server_opt: kind must be 0..3");
+    if (n < 0 || n_opt < 0 || n_opt > n) throw std::invalid_argument("server_opt: need 0 <= n_opt <= n");
+    if (n == 0) return;
+    if (!x || !anchor || !mom || (kind != 0 && !v)) throw std::invalid_argument("server_opt: null buffer");
+    if ((x | anchor | mom | v) % 16) throw std::invalid_argument("server_opt: buffers must be 16-byte aligned");
+    launch_server_opt(S(st), P<float>(x), P<float>(anchor), P<float>(mom), P<float>(v), n, n_opt, kind, lr, beta1,
+                      beta2, tau);
+    check_last("server_opt");
+  }, py::arg("stream"), py::arg("x"), py::arg("anchor"), py::arg("m"), py::arg("v"), py::arg("n"), py::arg("n_opt"),
+     py::arg("kind"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("tau"));
 
   // ---- compression ---------------------------------------------------------------
   m.def("topk_state_bytes", &topk_state_bytes);

@@ -27,6 +27,7 @@ ARCH = os.environ.get("FEDMI_OFFLOAD_ARCH", "gfx950")
 SOURCES = [
     CSRC / "kernels" / "lenet_kernels.hip",
     CSRC / "kernels" / "flat_ops.hip",
+    CSRC / "kernels" / "server_opt.hip",
     CSRC / "kernels" / "compress.hip",
     CSRC / "kernels" / "conv_igemm.hip",
     CSRC / "kernels" / "cnn_ops.hip",

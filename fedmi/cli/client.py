@@ -22,6 +22,7 @@ from ..engine.data import label_shard_indices, make_dataset
 from ..parallel.compress import make_compressor
 from ..parallel.fedavg import FedAvg
 from ..parallel.group import GroupManager
+from ..parallel.server_opt import add_server_opt_flags, make_server_opt
 from ..utils.metrics import MetricsLog, log
 
 
@@ -29,7 +30,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="fedmi federated client (one GPU)")
     ap.add_argument("-c", "--compressFlag", help="'Y': gzip gRPC + compressed FedAvg updates (int8 + error feedback)")
     ap.add_argument("-a", "--address", default="temp", help="listen address host:port (also the checkpoint name)")
-    ap.add_argument("-r", "--resume", action="store_true", help="resume from checkpoint/<address>.pth")
+    ap.add_argument("-r", "--resume", action="store_true",
+                    help="resume from checkpoint/<address>.pth (a --server-opt restarts its m / v from their "
+                         "initial values: the checkpoint format has no place for them)")
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--model", default="lenet")
     ap.add_argument("--device", default="auto")
@@ -57,6 +60,7 @@ def build_parser() -> argparse.ArgumentParser:
                          "fedmi.parallel.compress.DEFAULT_Y)")
     ap.add_argument("--topk-ratio", type=float, default=0.2)
     ap.add_argument("--compress-warmup", type=int, default=0, help="dense FedAvg rounds before -c Y compression starts")
+    add_server_opt_flags(ap)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--root", default=".")
     ap.add_argument("--metrics", default=None)
@@ -73,7 +77,10 @@ def pick_device(spec: str) -> torch.device:
 
 
 def main(argv=None) -> int:
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.server_opt != "none" and a.agg == "grpc":
+        ap.error("--server-opt needs --agg collective: with --agg grpc the coordinator averages (reference peers)")
     gzip = a.compressFlag == "Y"
     dev = pick_device(a.device)
     if dev.type == "cuda":
@@ -90,7 +97,9 @@ def main(argv=None) -> int:
     backend = a.backend if a.backend != "auto" else ("nccl" if dev.type == "cuda" else "gloo")
     transport = a.transport if a.transport != "auto" else ("auto" if dev.type == "cuda" else "dist")
     comp_kind = a.compress if a.compress is not None else ("Y" if gzip else "none")
-    fedavg = FedAvg(compressor=make_compressor(comp_kind, a.topk_ratio, trainer, a.compress_warmup))
+    fedavg = FedAvg(compressor=make_compressor(comp_kind, a.topk_ratio, trainer, a.compress_warmup),
+                    server_opt=make_server_opt(a.server_opt, trainer, a.server_lr, a.server_beta1, a.server_beta2,
+                                               a.server_tau))
     n = trainer.float_state().numel()
     cap = max(4 * n, 16 * (int(n * a.topk_ratio) + 64), n + 4 * (n // 256 + 64))
     group = GroupManager(backend, dev, timeout_s=a.collective_timeout, transport=transport, peer_capacity=cap,

@@ -114,6 +114,10 @@ class ClientAgent(P.TrainerServicer):
             c = ck.load(self.ckpt_path)
             trainer.load_state_dict(c["net"])
             self.round = int(c.get("epoch", 0))
+            if self.fedavg.server_opt is not None:
+                # the {'net','acc','epoch'} checkpoint carries no optimizer state: m and v restart from their
+                # initial values, anchored on the resumed model
+                self.fedavg.server_opt.reset(trainer)
             self._log(f"resumed from {self.ckpt_path} (epoch {self.round})")
         else:
             # reference bootstrap: persist the initial model (src/main.py:231-239)
@@ -168,6 +172,9 @@ class ClientAgent(P.TrainerServicer):
         self._round_start[0].copy_(fs, non_blocking=True)
         for d, b in zip(self._round_start[1], ints):
             d.copy_(b, non_blocking=True)
+        so = getattr(self.fedavg, "server_opt", None)
+        if so is not None:
+            so.snapshot()
 
     def _restore_round_start(self) -> Optional[float]:
         if self._round_start is None:
@@ -179,6 +186,9 @@ class ClientAgent(P.TrainerServicer):
         comp = getattr(self.fedavg, "compressor", None)
         if comp is not None:
             comp.reset(self.trainer)
+        so = getattr(self.fedavg, "server_opt", None)
+        if so is not None:
+            so.rollback()                       # the anchor is the restored model again; m, v as the round began
         return ck.state_digest(self.trainer.state_dict())
 
     def _reset_ready(self, epoch: int, data: bytes) -> None:
@@ -265,6 +275,8 @@ class ClientAgent(P.TrainerServicer):
                 self._probe("resync")
             elif changed and self.fedavg.compressor is not None:
                 self.fedavg.compressor.reset(self.trainer)
+                if self.fedavg.server_opt is not None:
+                    self.fedavg.server_opt.reset(self.trainer)
             rec0["group_ms"] = t.ms()
         lease_stats = []
         ck_epoch, message = -1, ""
@@ -408,6 +420,9 @@ class ClientAgent(P.TrainerServicer):
             comp = getattr(self.fedavg, "compressor", None)
             if comp is not None:
                 comp.reset(self.trainer)
+            so = getattr(self.fedavg, "server_opt", None)
+            if so is not None:
+                so.reset(self.trainer)          # the installed model is the previous global from now on
             self.writer.submit_bytes(self.ckpt_path, data)
             epoch = int(c.get("epoch", 0) or 0)
             self._reset_ready(epoch, data)

@@ -67,6 +67,11 @@ class LocalTrainer(abc.ABC):
     def float_state(self) -> torch.Tensor:
         """One flat fp32 tensor holding every averaged floating entry (params + float buffers)."""
 
+    def n_params(self) -> int:
+        """Number of leading entries of :meth:`float_state` that are trainable parameters (the rest are
+        floating buffers such as BN running statistics, which a server optimizer leaves a plain mean)."""
+        return self.float_state().numel()
+
     def int_state(self) -> List[torch.Tensor]:
         """Integer buffers (BN num_batches_tracked) averaged with truncation like the reference."""
         return []

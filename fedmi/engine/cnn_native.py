@@ -599,6 +599,9 @@ class CNNNativeTrainer(LocalTrainer):
     def float_state(self) -> torch.Tensor:
         return self.fs.flat
 
+    def n_params(self) -> int:
+        return self.fs.n_params
+
     def int_state(self) -> List[torch.Tensor]:
         return self.fs.int_state()
 

@@ -85,6 +85,11 @@ class _EFCompressor:
         self.global_ref.copy_(trainer.float_state())
         self.residual.zero_()
 
+    def reanchor(self, x: torch.Tensor) -> None:
+        """``x`` is the new global model on every client (a server optimizer moved it after the aggregation):
+        it becomes the anchor.  Unlike :meth:`reset` the error-feedback residual is kept."""
+        self.global_ref.copy_(x)
+
     def _dense(self, x: torch.Tensor, group, transport) -> bool:
         """Dense FedAvg of ``x`` while in warm-up; True if it ran (the anchor follows, residual empty)."""
         if self.dense_rounds >= self.warmup:

@@ -103,6 +103,7 @@ class FedAvg:
     transport: Optional[object] = None       # fedmi.parallel.peer.PeerAllReduce
     timer: AggregationTimer = field(default_factory=AggregationTimer)
     abort: Optional[threading.Event] = None  # the generation's loss flag (GroupManager.abort_event)
+    server_opt: Optional[object] = None      # fedmi.parallel.server_opt.ServerOpt (None: plain FedAvg)
 
     def world(self) -> int:
         if self.transport is not None:
@@ -120,6 +121,8 @@ class FedAvg:
             base = "rccl-allreduce" if be == "nccl" else f"{be}-allreduce"
         if self.compressor is not None and self.world() > 1:
             base += "+" + type(self.compressor).__name__.replace("Compressor", "").lower()
+        if self.server_opt is not None:
+            base += "+" + self.server_opt.cfg.kind
         return base
 
     def average(self, trainer: LocalTrainer) -> None:
@@ -139,6 +142,14 @@ class FedAvg:
         elif self.compressor is not None:
             # a client training alone holds the global model: it becomes the new anchor
             self.compressor.reset(trainer)
+        if self.server_opt is not None:
+            # the mean (at world 1: the client's own update) is the pseudo-gradient's end point; the step
+            # is replicated on every client, after the collective, on the trainer's stream
+            self.server_opt.step(trainer)
+            if self.compressor is not None:
+                # the clients compress against the model they all hold: the stepped one.  The residual is
+                # untransmitted update mass and stays.
+                self.compressor.reanchor(trainer.float_state())
         trainer.after_aggregate()
         dt = (time.perf_counter() - t0) * 1e3
         self.timer.last_ms = dt
@@ -157,6 +168,26 @@ class FedAvg:
             broadcast_state_(trainer, src, self.group, self.abort)
         if self.compressor is not None:
             self.compressor.reset(trainer)
+        if self.server_opt is not None:
+            self._resync_server_opt(trainer, src)
+
+    def _bcast(self, t: torch.Tensor, src: int) -> None:
+        if self.transport is not None:
+            if self.transport.world > 1:
+                self.transport.broadcast_(t, src)
+        elif _world(self.group) > 1:
+            _run(dist.broadcast, t, self.group, self.abort, src=src)
+
+    def _resync_server_opt(self, trainer: LocalTrainer, src: int) -> None:
+        """A (re)joining client gets rank ``src``'s optimizer state; the anchor is the model just installed.
+        Clients whose settings differ would drift apart silently, so the configuration is compared first."""
+        so = self.server_opt
+        cfg = so.cfg.as_vector().to(so.dev)
+        self._bcast(cfg, src)
+        so.check_config(cfg, src)
+        for t in so.state_tensors():
+            self._bcast(t, src)
+        so.reset(trainer)
 
 
 def eval_shard(test, rank: int, world: int):

@@ -54,6 +54,7 @@ def _run_seed(a, seed, data, dev, out) -> None:
     from fedmi.engine import build_trainer
     from fedmi.engine.base import TrainerConfig
     from fedmi.engine.data import contiguous_schedule, label_shard_indices, strided_schedule
+    from fedmi.parallel.server_opt import make_server_opt
 
     cfg = TrainerConfig(seed=seed, lr=a.lr, augment=not a.no_augment, use_graph=not a.no_graph)
     W = a.clients
@@ -75,6 +76,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
         else:
             tr.set_schedule(*strided_schedule(a.n_train, BATCH, r, W))
         clients.append(tr)
+    # one server optimizer for the simulated federation: it steps the stacked mean (held in client 0's state)
+    # before the result is copied into every client; parameter / buffer split from n_params()
+    server = make_server_opt(a.server_opt, clients[0], a.server_lr, a.server_beta1, a.server_beta2, a.server_tau)
     for rnd in range(1, a.rounds + 1):
         t0 = time.perf_counter()
         tstats = []
@@ -85,6 +89,10 @@ def _run_seed(a, seed, data, dev, out) -> None:
             mean = torch.stack([tr.float_state() for tr in clients]).mean(0)
             ints = [torch.div(sum(bs), W, rounding_mode="floor")
                     for bs in zip(*[[b.clone() for b in tr.int_state()] for tr in clients])]
+            if server is not None:
+                clients[0].float_state().copy_(mean)
+                server.step(clients[0])
+                mean = clients[0].float_state().clone()
             for tr in clients:
                 tr.float_state().copy_(mean)
                 for b, v in zip(tr.int_state(), ints):
@@ -97,7 +105,8 @@ def _run_seed(a, seed, data, dev, out) -> None:
         ev = clients[0].eval_stats()
         torch.cuda.synchronize() if dev.type == "cuda" else None
         rec = {"round": rnd, "engine": a.engine, "model": a.model, "clients": W, "lr": a.lr, "seed": seed,
-               "data": a.data,
+               "data": a.data, "server_opt": a.server_opt,
+               "server_lr": server.cfg.lr if server is not None else None,
                "deterministic": bool(a.deterministic),
                "augment": not a.no_augment, "graph": not a.no_graph,
                "split": f"noniid-{a.noniid}" if a.noniid else "strided-iid", "bn_eval": a.bn_eval,
@@ -134,6 +143,9 @@ def main() -> int:
                          "runs of the fp32 reference agree and a parity gap is the engine's, not reference noise")
     ap.add_argument("--bn-eval", choices=["running", "batch"], default="running",
                     help="batch: evaluate the global model with batch-statistics BN (diagnostic, PyTorch engines)")
+    from fedmi.parallel.server_opt import add_server_opt_flags
+
+    add_server_opt_flags(ap)
     a = ap.parse_args()
     if a.bn_eval == "batch" and a.engine == "native":
         ap.error("--bn-eval batch needs a PyTorch engine (fp32 / bf16)")
