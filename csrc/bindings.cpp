@@ -27,6 +27,9 @@ void set_ks1_diag(int);
 void launch_lenet_pack(hipStream_t, const float*, bf16*);
 void launch_sgd_flat(hipStream_t, float*, const float*, float*, long, float, float, float, float, int, int);
 void launch_server_opt(hipStream_t, float*, float*, float*, float*, long, long, int, float, float, float, float);
+void launch_drift_grad(hipStream_t, int, float*, const float*, const float*, const float*, float*, float, long);
+void launch_scaffold_finish(hipStream_t, const float*, float*, float*, long, long);
+void launch_scaffold_begin(hipStream_t, float*, const float*, const float*, float*, float*, long);
 void launch_ef_delta(hipStream_t, const float*, const float*, const float*, float*, long);
 size_t topk_state_bytes();
 size_t topk_overflow_offset();
@@ -168,6 +171,40 @@ static void fedmi_bind(py::module_& m) {
     check_last("server_opt");
   }, py::arg("stream"), py::arg("x"), py::arg("anchor"), py::arg("m"), py::arg("v"), py::arg("n"), py::arg("n_opt"),
      py::arg("kind"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("tau"));
+
+  // client-side drift correction of the flat gradient, between the backward pass and the SGD tail (kind: 0
+  // fedprox -- g, p, anchor, mu; 1 scaffold -- g, corr, acc); the other kind's buffers may be 0
+  m.def("drift_grad", [](uintptr_t st, int kind, uintptr_t g, uintptr_t p, uintptr_t anchor, uintptr_t corr,
+                         uintptr_t acc, float mu, long n) {
+    if (kind < 0 || kind > 1) throw std::invalid_argument("drift_grad: kind must be 0 (fedprox) or 1 (scaffold)");
+    if (n < 0) throw std::invalid_argument("drift_grad: need n >= 0");
+    if (n == 0) return;
+    if (!g || (kind == 0 ? (!p || !anchor) : (!corr || !acc))) throw std::invalid_argument("drift_grad: null buffer");
+    if ((g | p | anchor | corr | acc) % 16) throw std::invalid_argument("drift_grad: buffers must be 16-byte aligned");
+    launch_drift_grad(S(st), kind, P<float>(g), P<const float>(p), P<const float>(anchor), P<const float>(corr),
+                      P<float>(acc), mu, n);
+    check_last("drift_grad");
+  }, py::arg("stream"), py::arg("kind"), py::arg("g"), py::arg("p"), py::arg("anchor"), py::arg("corr"),
+     py::arg("acc"), py::arg("mu"), py::arg("n"));
+  m.def("scaffold_finish", [](uintptr_t st, uintptr_t acc, uintptr_t ci, uintptr_t delta, long K, long n) {
+    if (K < 1) throw std::invalid_argument("scaffold_finish: need K >= 1 (no SGD step was counted this round)");
+    if (n < 0) throw std::invalid_argument("scaffold_finish: need n >= 0");
+    if (n == 0) return;
+    if (!acc || !ci || !delta) throw std::invalid_argument("scaffold_finish: null buffer");
+    if ((acc | ci | delta) % 16) throw std::invalid_argument("scaffold_finish: buffers must be 16-byte aligned");
+    launch_scaffold_finish(S(st), P<const float>(acc), P<float>(ci), P<float>(delta), K, n);
+    check_last("scaffold_finish");
+  }, py::arg("stream"), py::arg("acc"), py::arg("ci"), py::arg("delta"), py::arg("K"), py::arg("n"));
+  m.def("scaffold_begin", [](uintptr_t st, uintptr_t c, uintptr_t dmean, uintptr_t ci, uintptr_t corr, uintptr_t acc,
+                             long n) {
+    if (n < 0) throw std::invalid_argument("scaffold_begin: need n >= 0");
+    if (n == 0) return;
+    if (!c || !dmean || !ci || !corr || !acc) throw std::invalid_argument("scaffold_begin: null buffer");
+    if ((c | dmean | ci | corr | acc) % 16) throw std::invalid_argument("scaffold_begin: buffers must be 16-byte aligned");
+    launch_scaffold_begin(S(st), P<float>(c), P<const float>(dmean), P<const float>(ci), P<float>(corr),
+                          P<float>(acc), n);
+    check_last("scaffold_begin");
+  }, py::arg("stream"), py::arg("c"), py::arg("dmean"), py::arg("ci"), py::arg("corr"), py::arg("acc"), py::arg("n"));
 
   // ---- compression ---------------------------------------------------------------
   m.def("topk_state_bytes", &topk_state_bytes);

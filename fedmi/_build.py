@@ -28,6 +28,7 @@ SOURCES = [
     CSRC / "kernels" / "lenet_kernels.hip",
     CSRC / "kernels" / "flat_ops.hip",
     CSRC / "kernels" / "server_opt.hip",
+    CSRC / "kernels" / "client_opt.hip",
     CSRC / "kernels" / "compress.hip",
     CSRC / "kernels" / "conv_igemm.hip",
     CSRC / "kernels" / "cnn_ops.hip",

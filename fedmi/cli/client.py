@@ -19,6 +19,7 @@ from ..control.client_agent import ClientAgent, serve_client
 from ..engine import build_trainer
 from ..engine.base import TrainerConfig
 from ..engine.data import label_shard_indices, make_dataset
+from ..parallel.client_opt import add_client_opt_flags, make_client_opt
 from ..parallel.compress import make_compressor
 from ..parallel.fedavg import FedAvg
 from ..parallel.group import GroupManager
@@ -32,7 +33,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-a", "--address", default="temp", help="listen address host:port (also the checkpoint name)")
     ap.add_argument("-r", "--resume", action="store_true",
                     help="resume from checkpoint/<address>.pth (a --server-opt restarts its m / v from their "
-                         "initial values: the checkpoint format has no place for them)")
+                         "initial values and a --client-opt its c / c_i at zero: the checkpoint format has no "
+                         "place for them)")
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--model", default="lenet")
     ap.add_argument("--device", default="auto")
@@ -61,6 +63,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--topk-ratio", type=float, default=0.2)
     ap.add_argument("--compress-warmup", type=int, default=0, help="dense FedAvg rounds before -c Y compression starts")
     add_server_opt_flags(ap)
+    add_client_opt_flags(ap)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--root", default=".")
     ap.add_argument("--metrics", default=None)
@@ -81,6 +84,11 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.server_opt != "none" and a.agg == "grpc":
         ap.error("--server-opt needs --agg collective: with --agg grpc the coordinator averages (reference peers)")
+    if a.client_opt != "none" and a.agg == "grpc":
+        ap.error("--client-opt needs --agg collective: with --agg grpc the coordinator averages the models only "
+                 "(reference peers), nothing carries scaffold's control variate or re-anchors fedprox")
+    if a.client_mu < 0:
+        ap.error("--client-mu must be >= 0")
     gzip = a.compressFlag == "Y"
     dev = pick_device(a.device)
     if dev.type == "cuda":
@@ -97,7 +105,14 @@ def main(argv=None) -> int:
     backend = a.backend if a.backend != "auto" else ("nccl" if dev.type == "cuda" else "gloo")
     transport = a.transport if a.transport != "auto" else ("auto" if dev.type == "cuda" else "dist")
     comp_kind = a.compress if a.compress is not None else ("Y" if gzip else "none")
+    try:
+        client_opt = make_client_opt(a.client_opt, trainer, a.client_mu)
+    except NotImplementedError as e:
+        ap.error(f"--client-opt {a.client_opt} is not available for --model {a.model} on this engine: {e}"
+                 + ("; FEDMI_TORCH_PATH=1 runs LeNet on the PyTorch engine, which has the hook"
+                    if a.model.lower() == "lenet" else ""))
     fedavg = FedAvg(compressor=make_compressor(comp_kind, a.topk_ratio, trainer, a.compress_warmup),
+                    client_opt=client_opt,
                     server_opt=make_server_opt(a.server_opt, trainer, a.server_lr, a.server_beta1, a.server_beta2,
                                                a.server_tau))
     n = trainer.float_state().numel()

@@ -118,6 +118,9 @@ class ClientAgent(P.TrainerServicer):
                 # the {'net','acc','epoch'} checkpoint carries no optimizer state: m and v restart from their
                 # initial values, anchored on the resumed model
                 self.fedavg.server_opt.reset(trainer)
+            if getattr(self.fedavg, "client_opt", None) is not None:
+                # nor any client-optimizer state: c and c_i restart at zero, anchored on the resumed model
+                self.fedavg.client_opt.reset(trainer)
             self._log(f"resumed from {self.ckpt_path} (epoch {self.round})")
         else:
             # reference bootstrap: persist the initial model (src/main.py:231-239)
@@ -175,6 +178,9 @@ class ClientAgent(P.TrainerServicer):
         so = getattr(self.fedavg, "server_opt", None)
         if so is not None:
             so.snapshot()
+        co = getattr(self.fedavg, "client_opt", None)
+        if co is not None:
+            co.snapshot()
 
     def _restore_round_start(self) -> Optional[float]:
         if self._round_start is None:
@@ -189,6 +195,9 @@ class ClientAgent(P.TrainerServicer):
         so = getattr(self.fedavg, "server_opt", None)
         if so is not None:
             so.rollback()                       # the anchor is the restored model again; m, v as the round began
+        co = getattr(self.fedavg, "client_opt", None)
+        if co is not None:
+            co.rollback()                       # anchor / c, c_i, corr as the round began; the void epoch's sum dropped
         return ck.state_digest(self.trainer.state_dict())
 
     def _reset_ready(self, epoch: int, data: bytes) -> None:
@@ -277,6 +286,8 @@ class ClientAgent(P.TrainerServicer):
                 self.fedavg.compressor.reset(self.trainer)
                 if self.fedavg.server_opt is not None:
                     self.fedavg.server_opt.reset(self.trainer)
+                if getattr(self.fedavg, "client_opt", None) is not None:
+                    self.fedavg.client_opt.reset(self.trainer)
             rec0["group_ms"] = t.ms()
         lease_stats = []
         ck_epoch, message = -1, ""
@@ -423,6 +434,9 @@ class ClientAgent(P.TrainerServicer):
             so = getattr(self.fedavg, "server_opt", None)
             if so is not None:
                 so.reset(self.trainer)          # the installed model is the previous global from now on
+            co = getattr(self.fedavg, "client_opt", None)
+            if co is not None:
+                co.reset(self.trainer)          # the installed model is the round's starting point (fedprox anchor)
             self.writer.submit_bytes(self.ckpt_path, data)
             epoch = int(c.get("epoch", 0) or 0)
             self._reset_ready(epoch, data)

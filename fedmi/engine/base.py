@@ -76,6 +76,13 @@ class LocalTrainer(abc.ABC):
         """Integer buffers (BN num_batches_tracked) averaged with truncation like the reference."""
         return []
 
+    def set_client_opt(self, co) -> None:
+        """Attach a :class:`fedmi.parallel.client_opt.ClientOpt` (None detaches): an engine that supports it calls
+        ``co.apply(grad, params)`` between the backward pass and the SGD tail of every step and
+        ``co.count(steps)`` once per epoch.  Needs a materialised flat gradient, so it is opt-in per engine."""
+        raise NotImplementedError(f"{type(self).__name__} has no client-optimizer hook (no flat gradient between "
+                                  "the backward pass and the SGD update)")
+
     def after_aggregate(self) -> None:
         """Called after float_state() was overwritten (FedAvg / load)."""
 

@@ -570,6 +570,7 @@ class CNNNativeTrainer(LocalTrainer):
         self._starts: List[int] = []
         self._sizes: List[int] = []
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
+        self._client_opt = None
         self.round_idx = 0
         self.pack()
         # the step's tail in ONE launch: SGD on the flat master + every conv's forward / DGRAD image from the
@@ -614,6 +615,10 @@ class CNNNativeTrainer(LocalTrainer):
     def set_lr(self, lr: float) -> None:
         self.cfg.lr = float(lr)
         self._graphs.clear()
+
+    def set_client_opt(self, co) -> None:
+        self._client_opt = co
+        self._graphs.clear()               # the correction is (or is no longer) part of the captured step
 
     def pack(self) -> None:
         conv.pack_weights([it for it in (u.pack_item() for u in self.units) if it is not None])
@@ -931,6 +936,8 @@ class CNNNativeTrainer(LocalTrainer):
         """One SGD step on the batch at sched[counter] (device-side)."""
         cnn.sched_next(self.sched, self.counter, self.cur, zero=self.stats_all)
         self._forward_backward(nb, zeroed=True)
+        if self._client_opt is not None:   # drift correction of the finished flat gradient; the tail is unchanged
+            self._client_opt.apply(self.fs.grad, self.fs.params)
         self._sgd()
 
     def grads_for_batch(self, start: int, nb: int) -> None:
@@ -955,13 +962,16 @@ class CNNNativeTrainer(LocalTrainer):
                 if g is None:
                     g = self._capture(nb)
                 g.replay()
+        if self._client_opt is not None:
+            self._client_opt.count(len(self._sizes))
         self.round_ctr[0] += 1
         self.round_idx += 1
 
     def _capture(self, nb: int) -> torch.cuda.CUDAGraph:
         # a warm-up eager step precedes capture; snapshot and restore everything it touches
         saved = (self.fs.flat.clone(), self.fs.mom.clone(), [b.clone() for b in self.int_state()],
-                 self.counter.clone(), self.stats.clone(), [u.shift.clone() for u in self.units])
+                 self.counter.clone(), self.stats.clone(), [u.shift.clone() for u in self.units],
+                 None if self._client_opt is None else self._client_opt.save_acc())
         s = torch.cuda.Stream(self._device)
         s.wait_stream(torch.cuda.current_stream(self._device))
         with torch.cuda.stream(s):
@@ -979,6 +989,8 @@ class CNNNativeTrainer(LocalTrainer):
             self.stats.copy_(saved[4])
             for u, v in zip(self.units, saved[5]):      # BN statistics shifts: the replay starts bit-identical
                 u.shift.copy_(v)
+            if self._client_opt is not None:            # the warm-up's raw gradient must not end up in c_i
+                self._client_opt.restore_acc(saved[6])
         self.pack()
         self._graphs[("train", nb)] = g
         return g

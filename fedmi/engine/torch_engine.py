@@ -139,6 +139,7 @@ class TorchTrainer(LocalTrainer):
         self.use_graph = bool(self.hybrid and cfg.use_graph and os.environ.get("FEDMI_HYBRID_GRAPH", "1") == "1")
         self._graph = None
         self._gx = self._gy = None
+        self._client_opt = None
 
     @property
     def device(self) -> torch.device:
@@ -166,6 +167,10 @@ class TorchTrainer(LocalTrainer):
 
     def momentum_state(self) -> torch.Tensor:
         return self.fs.mom
+
+    def set_client_opt(self, co) -> None:
+        self._client_opt = co
+        self._graph = None                 # the correction is (or is no longer) part of the captured step
 
     # ---- data ----------------------------------------------------------------------
     def set_schedule(self, starts, sizes) -> None:
@@ -221,7 +226,8 @@ class TorchTrainer(LocalTrainer):
         afterwards, so capturing never changes the training trajectory."""
         fs = self.fs
         self._gx, self._gy = x.clone(), y.clone()
-        snap = (fs.flat.clone(), fs.mom.clone(), [b.clone() for b in self.int_state()], self._tstats.clone())
+        snap = (fs.flat.clone(), fs.mom.clone(), [b.clone() for b in self.int_state()], self._tstats.clone(),
+                None if self._client_opt is None else self._client_opt.save_acc())
         side = torch.cuda.Stream(self._device)
         side.wait_stream(torch.cuda.current_stream(self._device))
         with torch.cuda.stream(side):
@@ -236,12 +242,18 @@ class TorchTrainer(LocalTrainer):
             for b, v in zip(self.int_state(), snap[2]):
                 b.copy_(v)
             self._tstats.copy_(snap[3])
+            if self._client_opt is not None:   # the warm-up's raw gradient must not end up in c_i
+                self._client_opt.restore_acc(snap[4])
         self._graph = g
         # the graph holds raw pointers into the shared conv workspace: keep that allocation alive even if a
         # later eager call (eval at a larger batch) grows the workspace and drops it from the cache
         from ..ops import conv as _conv
 
         self._graph_ws = _conv._WS.get(self._device)
+
+    def _drift(self) -> None:
+        if self._client_opt is not None:   # drift correction of the finished flat gradient; the update is unchanged
+            self._client_opt.apply(self.fs.grad, self.fs.params)
 
     def _step_body(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         nb = x.shape[0]
@@ -259,6 +271,7 @@ class TorchTrainer(LocalTrainer):
                     if p.grad is not None and p.grad.data_ptr() != g.data_ptr():
                         g.copy_(p.grad)       # a gradient not produced in place (classifier GEMM, ATen op)
                     p.grad = g
+            self._drift()
             self._sgd()
             ce_stats_(out.detach(), y, self._tstats)
             return loss
@@ -266,6 +279,7 @@ class TorchTrainer(LocalTrainer):
         out = self._run(x)
         loss = F.cross_entropy(out, y)
         loss.backward()
+        self._drift()
         self._sgd()
         with torch.no_grad():
             self._tstats[0] += loss.detach().double() * nb
@@ -278,6 +292,8 @@ class TorchTrainer(LocalTrainer):
         self._tstats.zero_()
         for s, n in zip(self._starts, self._sizes):
             self.train_step(s, n)
+        if self._client_opt is not None:
+            self._client_opt.count(len(self._sizes))
         if self._starts:
             self.round_idx += 1
 

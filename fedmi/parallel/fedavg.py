@@ -104,6 +104,7 @@ class FedAvg:
     timer: AggregationTimer = field(default_factory=AggregationTimer)
     abort: Optional[threading.Event] = None  # the generation's loss flag (GroupManager.abort_event)
     server_opt: Optional[object] = None      # fedmi.parallel.server_opt.ServerOpt (None: plain FedAvg)
+    client_opt: Optional[object] = None      # fedmi.parallel.client_opt.ClientOpt (None: plain local SGD)
 
     def world(self) -> int:
         if self.transport is not None:
@@ -123,10 +124,15 @@ class FedAvg:
             base += "+" + type(self.compressor).__name__.replace("Compressor", "").lower()
         if self.server_opt is not None:
             base += "+" + self.server_opt.cfg.kind
+        if self.client_opt is not None:
+            base += "+" + self.client_opt.cfg.kind
         return base
 
     def average(self, trainer: LocalTrainer) -> None:
         t0 = time.perf_counter()
+        co = self.client_opt
+        if co is not None:
+            co.finish_round()                 # scaffold: c_i = the epoch's mean raw gradient, delta = its change
         if self.world() > 1:
             if self.compressor is not None:
                 self.compressor.aggregate(trainer, self.group, transport=self.transport)
@@ -139,6 +145,13 @@ class FedAvg:
                     self.transport.allreduce_mean_(b)
                 else:
                     allreduce_int_mean_(b, self.group, self.abort)
+            if co is not None and co.delta is not None:
+                # scaffold's second quantity: same transport, group and abort flag as the model, always dense
+                # (also with -c Y); the mean is the same bits on every rank, so c stays replicated
+                if self.transport is not None:
+                    self.transport.allreduce_mean_(co.delta)
+                else:
+                    allreduce_mean_(co.delta, self.group, self.abort)
         elif self.compressor is not None:
             # a client training alone holds the global model: it becomes the new anchor
             self.compressor.reset(trainer)
@@ -150,6 +163,10 @@ class FedAvg:
                 # the clients compress against the model they all hold: the stepped one.  The residual is
                 # untransmitted update mass and stays.
                 self.compressor.reanchor(trainer.float_state())
+        if co is not None:
+            # float_state() is the next round's starting model (fedprox anchor); at world 1 the client's own
+            # delta is the mean
+            co.begin_round(trainer, co.delta)
         trainer.after_aggregate()
         dt = (time.perf_counter() - t0) * 1e3
         self.timer.last_ms = dt
@@ -170,6 +187,8 @@ class FedAvg:
             self.compressor.reset(trainer)
         if self.server_opt is not None:
             self._resync_server_opt(trainer, src)
+        if self.client_opt is not None:
+            self._resync_server_opt(trainer, src, self.client_opt)
 
     def _bcast(self, t: torch.Tensor, src: int) -> None:
         if self.transport is not None:
@@ -178,10 +197,11 @@ class FedAvg:
         elif _world(self.group) > 1:
             _run(dist.broadcast, t, self.group, self.abort, src=src)
 
-    def _resync_server_opt(self, trainer: LocalTrainer, src: int) -> None:
+    def _resync_server_opt(self, trainer: LocalTrainer, src: int, so=None) -> None:
         """A (re)joining client gets rank ``src``'s optimizer state; the anchor is the model just installed.
-        Clients whose settings differ would drift apart silently, so the configuration is compared first."""
-        so = self.server_opt
+        Clients whose settings differ would drift apart silently, so the configuration is compared first.
+        ``so``: the server optimizer, or the client optimizer (same hand-over: its replicated ``c``)."""
+        so = self.server_opt if so is None else so
         cfg = so.cfg.as_vector().to(so.dev)
         self._bcast(cfg, src)
         so.check_config(cfg, src)

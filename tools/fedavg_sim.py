@@ -54,6 +54,7 @@ def _run_seed(a, seed, data, dev, out) -> None:
     from fedmi.engine import build_trainer
     from fedmi.engine.base import TrainerConfig
     from fedmi.engine.data import contiguous_schedule, label_shard_indices, strided_schedule
+    from fedmi.parallel.client_opt import make_client_opt
     from fedmi.parallel.server_opt import make_server_opt
 
     cfg = TrainerConfig(seed=seed, lr=a.lr, augment=not a.no_augment, use_graph=not a.no_graph)
@@ -79,6 +80,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
     # one server optimizer for the simulated federation: it steps the stacked mean (held in client 0's state)
     # before the result is copied into every client; parameter / buffer split from n_params()
     server = make_server_opt(a.server_opt, clients[0], a.server_lr, a.server_beta1, a.server_beta2, a.server_tau)
+    # one client optimizer per simulated client (its own c_i / anchor); the mean of their delta stands in for
+    # the second all-reduce
+    copts = [make_client_opt(a.client_opt, tr, a.client_mu) for tr in clients]
     for rnd in range(1, a.rounds + 1):
         t0 = time.perf_counter()
         tstats = []
@@ -86,6 +90,12 @@ def _run_seed(a, seed, data, dev, out) -> None:
             tr.train_epoch()
             tstats.append(tr.train_stats())
         with torch.no_grad():
+            dmean = None
+            if copts[0] is not None:
+                for co in copts:
+                    co.finish_round()
+                if copts[0].delta is not None:
+                    dmean = torch.stack([co.delta for co in copts]).mean(0)
             mean = torch.stack([tr.float_state() for tr in clients]).mean(0)
             ints = [torch.div(sum(bs), W, rounding_mode="floor")
                     for bs in zip(*[[b.clone() for b in tr.int_state()] for tr in clients])]
@@ -98,6 +108,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
                 for b, v in zip(tr.int_state(), ints):
                     b.copy_(v)
                 tr.after_aggregate()
+            for tr, co in zip(clients, copts):
+                if co is not None:
+                    co.begin_round(tr, dmean)
         if a.bn_eval == "batch":
             _eval_batch_bn(clients[0])
         else:
@@ -107,6 +120,7 @@ def _run_seed(a, seed, data, dev, out) -> None:
         rec = {"round": rnd, "engine": a.engine, "model": a.model, "clients": W, "lr": a.lr, "seed": seed,
                "data": a.data, "server_opt": a.server_opt,
                "server_lr": server.cfg.lr if server is not None else None,
+               "client_opt": a.client_opt, "client_mu": a.client_mu if a.client_opt == "fedprox" else None,
                "deterministic": bool(a.deterministic),
                "augment": not a.no_augment, "graph": not a.no_graph,
                "split": f"noniid-{a.noniid}" if a.noniid else "strided-iid", "bn_eval": a.bn_eval,
@@ -146,7 +160,12 @@ def main() -> int:
     from fedmi.parallel.server_opt import add_server_opt_flags
 
     add_server_opt_flags(ap)
+    from fedmi.parallel.client_opt import add_client_opt_flags
+
+    add_client_opt_flags(ap)
     a = ap.parse_args()
+    if a.client_mu < 0:
+        ap.error("--client-mu must be >= 0")
     if a.bn_eval == "batch" and a.engine == "native":
         ap.error("--bn-eval batch needs a PyTorch engine (fp32 / bf16)")
     if a.engine in ("fp32", "bf16"):
