@@ -1306,7 +1306,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const bf16* __restrict__
 // ---------------------------------------------------------------------------
 // Fused SGD step + weight images (the CNN engines' per-step tail): one launch updates every parameter of the
 // flat fp32 master (torch.optim.SGD with momentum / weight decay, fedmi::sgd_elem -- bit-identical to
-// sgd_flat_kernel) and, for each dense conv, writes the forward image wr[o][r][s][c] and the DGRAD phase
+// sgd_flat) and, for each dense conv, writes the forward image wr[o][r][s][c] and the DGRAD phase
 // images wd[c][i][j][o] from the UPDATED values while they are still in LDS.  The unfused tail read the fp32
 // weights three times (sgd_flat, conv_pack_multi, dgrad_pack) in 3-4 launches.
 // Workgroup = one conv block of 64 filters x cb input channels (dgrad_pack_kernel's tiling: the image rows

@@ -114,13 +114,9 @@ class ClientAgent(P.TrainerServicer):
             c = ck.load(self.ckpt_path)
             trainer.load_state_dict(c["net"])
             self.round = int(c.get("epoch", 0))
-            if self.fedavg.server_opt is not None:
-                # the {'net','acc','epoch'} checkpoint carries no optimizer state: m and v restart from their
-                # initial values, anchored on the resumed model
-                self.fedavg.server_opt.reset(trainer)
-            if getattr(self.fedavg, "client_opt", None) is not None:
-                # nor any client-optimizer state: c and c_i restart at zero, anchored on the resumed model
-                self.fedavg.client_opt.reset(trainer)
+            # the {'net','acc','epoch'} checkpoint carries no optimizer state: m and v restart from their initial
+            # values and c and c_i at zero, anchored on the resumed model
+            self.fedavg.reset_opts(trainer)
             self._log(f"resumed from {self.ckpt_path} (epoch {self.round})")
         else:
             # reference bootstrap: persist the initial model (src/main.py:231-239)
@@ -175,12 +171,7 @@ class ClientAgent(P.TrainerServicer):
         self._round_start[0].copy_(fs, non_blocking=True)
         for d, b in zip(self._round_start[1], ints):
             d.copy_(b, non_blocking=True)
-        so = getattr(self.fedavg, "server_opt", None)
-        if so is not None:
-            so.snapshot()
-        co = getattr(self.fedavg, "client_opt", None)
-        if co is not None:
-            co.snapshot()
+        self.fedavg.snapshot_opts()
 
     def _restore_round_start(self) -> Optional[float]:
         if self._round_start is None:
@@ -192,12 +183,9 @@ class ClientAgent(P.TrainerServicer):
         comp = getattr(self.fedavg, "compressor", None)
         if comp is not None:
             comp.reset(self.trainer)
-        so = getattr(self.fedavg, "server_opt", None)
-        if so is not None:
-            so.rollback()                       # the anchor is the restored model again; m, v as the round began
-        co = getattr(self.fedavg, "client_opt", None)
-        if co is not None:
-            co.rollback()                       # anchor / c, c_i, corr as the round began; the void epoch's sum dropped
+        # the anchors are the restored model again; m, v and c, c_i, corr as the round began, the void epoch's
+        # gradient sum dropped
+        self.fedavg.rollback_opts()
         return ck.state_digest(self.trainer.state_dict())
 
     def _reset_ready(self, epoch: int, data: bytes) -> None:
@@ -284,10 +272,7 @@ class ClientAgent(P.TrainerServicer):
                 self._probe("resync")
             elif changed and self.fedavg.compressor is not None:
                 self.fedavg.compressor.reset(self.trainer)
-                if self.fedavg.server_opt is not None:
-                    self.fedavg.server_opt.reset(self.trainer)
-                if getattr(self.fedavg, "client_opt", None) is not None:
-                    self.fedavg.client_opt.reset(self.trainer)
+                self.fedavg.reset_opts(self.trainer)
             rec0["group_ms"] = t.ms()
         lease_stats = []
         ck_epoch, message = -1, ""
@@ -431,12 +416,8 @@ class ClientAgent(P.TrainerServicer):
             comp = getattr(self.fedavg, "compressor", None)
             if comp is not None:
                 comp.reset(self.trainer)
-            so = getattr(self.fedavg, "server_opt", None)
-            if so is not None:
-                so.reset(self.trainer)          # the installed model is the previous global from now on
-            co = getattr(self.fedavg, "client_opt", None)
-            if co is not None:
-                co.reset(self.trainer)          # the installed model is the round's starting point (fedprox anchor)
+            # the installed model is the previous global and the round's starting point (fedprox anchor) from now on
+            self.fedavg.reset_opts(self.trainer)
             self.writer.submit_bytes(self.ckpt_path, data)
             epoch = int(c.get("epoch", 0) or 0)
             self._reset_ready(epoch, data)

@@ -30,6 +30,7 @@ from typing import List, Optional
 import torch
 
 from .. import native
+from .replicated import ReplicatedConfig, ReplicatedState
 
 KINDS = ("fedprox", "scaffold")      # index == the kernels' ``kind`` argument
 
@@ -39,9 +40,13 @@ def _f32(s: float) -> float:
 
 
 @dataclass
-class ClientOptConfig:
+class ClientOptConfig(ReplicatedConfig):
     kind: str
     mu: float = 0.01                 # FedProx's proximal weight (unused by scaffold)
+
+    KINDS = KINDS
+    FIELDS = ("kind", "mu")
+    ROLE, FLAG = "client optimizer", "--client-opt"
 
     def __post_init__(self):
         if self.kind not in KINDS:
@@ -49,16 +54,6 @@ class ClientOptConfig:
         self.mu = float(self.mu)
         if not self.mu >= 0:
             raise ValueError("client optimizer: mu must be >= 0")
-
-    @property
-    def kind_id(self) -> int:
-        return KINDS.index(self.kind)
-
-    FIELDS = ("kind", "mu")
-
-    def as_vector(self) -> torch.Tensor:
-        """(kind id, mu) in fp64: what :meth:`FedAvg.resync` compares across clients."""
-        return torch.tensor([self.kind_id, self.mu], dtype=torch.float64)
 
 
 def fma32(a: float, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -104,17 +99,16 @@ def reference_begin(c: torch.Tensor, dmean: torch.Tensor, ci: torch.Tensor, dtyp
     return cn, cn - ci.to(dtype), torch.zeros_like(cn)
 
 
-class ClientOpt:
+class ClientOpt(ReplicatedState):
     """Drift-correction state of one client.  FedProx: ``anchor``.  SCAFFOLD: ``c`` (replicated), ``ci``,
     ``corr = c - ci``, the raw-gradient sum ``acc``, the round's ``delta``, and the host step count ``K``."""
 
     def __init__(self, trainer, cfg: ClientOptConfig):
         x = trainer.float_state()
-        self.cfg = cfg
+        super().__init__(x, cfg)
         self.n = int(trainer.n_params())
         if not 0 <= self.n <= x.numel():
             raise ValueError(f"n_params() = {self.n} outside the float state of {x.numel()} entries")
-        self.dev = x.device
         self.anchor = self.c = self.ci = self.corr = self.acc = self.delta = None
         if cfg.kind == "fedprox":
             self.anchor = x[:self.n].detach().clone()
@@ -122,8 +116,6 @@ class ClientOpt:
             self.c, self.ci, self.corr, self.acc, self.delta = (
                 torch.zeros(self.n, dtype=torch.float32, device=self.dev) for _ in range(5))
         self.K = 0
-        self._nat = native.require() if x.is_cuda else None
-        self._snap = None
 
     def _stream(self) -> int:
         return native.stream_handle(self.dev)
@@ -212,20 +204,8 @@ class ClientOpt:
             self.acc.zero_()
         self.K = 0
 
-    def snapshot(self) -> None:
-        """Device copy of ``anchor`` / ``c``, ``ci``, ``corr`` (the client agent takes it at the start of every round)."""
-        if self._snap is None:
-            self._snap = tuple(torch.empty_like(t) for t in self._rolled())
-        for d, s in zip(self._snap, self._rolled()):
-            d.copy_(s, non_blocking=True)
-
-    def rollback(self) -> None:
-        """Back to the last :meth:`snapshot`, bit for bit; ``acc`` and ``K`` restart from zero (a void round's
-        gradients must not leave a trace in ``ci``)."""
-        if self._snap is None:
-            raise RuntimeError("ClientOpt.rollback() without a snapshot()")
-        for d, s in zip(self._rolled(), self._snap):
-            d.copy_(s)
+    def _after_rollback(self) -> None:
+        """``acc`` and ``K`` restart from zero (a void round's gradients must not leave a trace in ``ci``)."""
         if self.acc is not None:
             self.acc.zero_()
         self.K = 0
@@ -233,17 +213,6 @@ class ClientOpt:
     def state_tensors(self) -> List[torch.Tensor]:
         """What a joining client must receive from the survivors: ``c``.  Its own ``ci`` starts at zero."""
         return [] if self.c is None else [self.c]
-
-    def check_config(self, other: torch.Tensor, src: int) -> None:
-        """Raise if rank ``src``'s configuration (:meth:`ClientOptConfig.as_vector`) differs from the local one."""
-        mine = self.cfg.as_vector()
-        other = other.detach().cpu().to(torch.float64)
-        for i, name in enumerate(ClientOptConfig.FIELDS):
-            if float(mine[i]) != float(other[i]):
-                show = (lambda t: KINDS[int(t)] if 0 <= int(t) < len(KINDS) else int(t)) if i == 0 else float
-                raise RuntimeError(f"client optimizer configuration differs from rank {src}'s in {name!r}: "
-                                   f"local {show(mine[i])}, rank {src} {show(other[i])} -- every client must run "
-                                   "the same --client-opt settings")
 
 
 def add_client_opt_flags(ap) -> None:

@@ -74,12 +74,7 @@ def allreduce_int_mean_(t: torch.Tensor, group=None, abort: Optional[threading.E
 
 def broadcast_state_(trainer: LocalTrainer, src: int = 0, group=None, abort: Optional[threading.Event] = None) -> None:
     """Give every client rank ``src``'s model (fixes reference quirk A7: independent random inits)."""
-    if _world(group) == 1:
-        return
-    _run(dist.broadcast, trainer.float_state(), group, abort, src=src)
-    for b in trainer.int_state():
-        _run(dist.broadcast, b, group, abort, src=src)
-    trainer.after_aggregate()
+    FedAvg(group=group, abort=abort).resync(trainer, src)
 
 
 @dataclass
@@ -122,11 +117,32 @@ class FedAvg:
             base = "rccl-allreduce" if be == "nccl" else f"{be}-allreduce"
         if self.compressor is not None and self.world() > 1:
             base += "+" + type(self.compressor).__name__.replace("Compressor", "").lower()
-        if self.server_opt is not None:
-            base += "+" + self.server_opt.cfg.kind
-        if self.client_opt is not None:
-            base += "+" + self.client_opt.cfg.kind
+        for o in self.opts():
+            base += "+" + o.cfg.kind
         return base
+
+    def opts(self) -> list:
+        """The attached optimizers (:class:`fedmi.parallel.replicated.ReplicatedState`): server, then client."""
+        return [o for o in (self.server_opt, self.client_opt) if o is not None]
+
+    def snapshot_opts(self) -> None:
+        for o in self.opts():
+            o.snapshot()
+
+    def rollback_opts(self) -> None:
+        for o in self.opts():
+            o.rollback()
+
+    def reset_opts(self, trainer: LocalTrainer) -> None:
+        for o in self.opts():
+            o.reset(trainer)
+
+    def _mean(self, t: torch.Tensor, ints: bool = False) -> None:
+        """In-place mean over the group: the peer transport, else ``torch.distributed`` (``ints``: floor-divided)."""
+        if self.transport is not None:
+            self.transport.allreduce_mean_(t)
+        else:
+            (allreduce_int_mean_ if ints else allreduce_mean_)(t, self.group, self.abort)
 
     def average(self, trainer: LocalTrainer) -> None:
         t0 = time.perf_counter()
@@ -136,22 +152,14 @@ class FedAvg:
         if self.world() > 1:
             if self.compressor is not None:
                 self.compressor.aggregate(trainer, self.group, transport=self.transport)
-            elif self.transport is not None:
-                self.transport.allreduce_mean_(trainer.float_state())
             else:
-                allreduce_mean_(trainer.float_state(), self.group, self.abort)
+                self._mean(trainer.float_state())
             for b in trainer.int_state():
-                if self.transport is not None:
-                    self.transport.allreduce_mean_(b)
-                else:
-                    allreduce_int_mean_(b, self.group, self.abort)
+                self._mean(b, ints=True)
             if co is not None and co.delta is not None:
                 # scaffold's second quantity: same transport, group and abort flag as the model, always dense
                 # (also with -c Y); the mean is the same bits on every rank, so c stays replicated
-                if self.transport is not None:
-                    self.transport.allreduce_mean_(co.delta)
-                else:
-                    allreduce_mean_(co.delta, self.group, self.abort)
+                self._mean(co.delta)
         elif self.compressor is not None:
             # a client training alone holds the global model: it becomes the new anchor
             self.compressor.reset(trainer)
@@ -175,20 +183,15 @@ class FedAvg:
 
     def resync(self, trainer: LocalTrainer, src: int = 0) -> None:
         """Everyone adopts rank ``src``'s model (init, or after an aborted round) and re-anchors."""
-        if self.transport is not None:
-            if self.transport.world > 1:
-                self.transport.broadcast_(trainer.float_state(), src)
-                for b in trainer.int_state():
-                    self.transport.broadcast_(b, src)
+        self._bcast(trainer.float_state(), src)
+        for b in trainer.int_state():
+            self._bcast(b, src)
+        if self.transport is not None or self.world() > 1:   # as ever: not at world 1 over torch.distributed
             trainer.after_aggregate()
-        else:
-            broadcast_state_(trainer, src, self.group, self.abort)
         if self.compressor is not None:
             self.compressor.reset(trainer)
-        if self.server_opt is not None:
-            self._resync_server_opt(trainer, src)
-        if self.client_opt is not None:
-            self._resync_server_opt(trainer, src, self.client_opt)
+        for o in self.opts():
+            self._hand_over(o, trainer, src)
 
     def _bcast(self, t: torch.Tensor, src: int) -> None:
         if self.transport is not None:
@@ -197,17 +200,16 @@ class FedAvg:
         elif _world(self.group) > 1:
             _run(dist.broadcast, t, self.group, self.abort, src=src)
 
-    def _resync_server_opt(self, trainer: LocalTrainer, src: int, so=None) -> None:
-        """A (re)joining client gets rank ``src``'s optimizer state; the anchor is the model just installed.
-        Clients whose settings differ would drift apart silently, so the configuration is compared first.
-        ``so``: the server optimizer, or the client optimizer (same hand-over: its replicated ``c``)."""
-        so = self.server_opt if so is None else so
-        cfg = so.cfg.as_vector().to(so.dev)
+    def _hand_over(self, opt, trainer: LocalTrainer, src: int) -> None:
+        """A (re)joining client gets rank ``src``'s state of one optimizer (``m`` and ``v``, or the replicated
+        ``c``); the anchor is the model just installed.  Clients whose settings differ would drift apart silently,
+        so the configuration is compared first."""
+        cfg = opt.cfg.as_vector().to(opt.dev)
         self._bcast(cfg, src)
-        so.check_config(cfg, src)
-        for t in so.state_tensors():
+        opt.check_config(cfg, src)
+        for t in opt.state_tensors():
             self._bcast(t, src)
-        so.reset(trainer)
+        opt.reset(trainer)
 
 
 def eval_shard(test, rank: int, world: int):

@@ -29,18 +29,23 @@ from typing import List, Optional
 import torch
 
 from .. import native
+from .replicated import ReplicatedConfig, ReplicatedState
 
 KINDS = ("fedavgm", "fedadagrad", "fedyogi", "fedadam")      # index == the kernel's ``kind`` argument
 DEFAULT_LR = {"fedavgm": 1.0, "fedadagrad": 0.01, "fedyogi": 0.01, "fedadam": 0.01}   # the papers' starting points
 
 
 @dataclass
-class ServerOptConfig:
+class ServerOptConfig(ReplicatedConfig):
     kind: str
     lr: Optional[float] = None       # None: DEFAULT_LR[kind]
     beta1: float = 0.9
     beta2: float = 0.99
     tau: float = 1e-3
+
+    KINDS = KINDS
+    FIELDS = ("kind", "lr", "beta1", "beta2", "tau")
+    ROLE, FLAG, MISMATCH_TAIL = "server optimizer", "--server-opt", ", or the replicated state drifts apart"
 
     def __post_init__(self):
         if self.kind not in KINDS:
@@ -49,16 +54,6 @@ class ServerOptConfig:
         self.beta1, self.beta2, self.tau = float(self.beta1), float(self.beta2), float(self.tau)
         if self.tau <= 0:
             raise ValueError("server optimizer: tau must be > 0")
-
-    @property
-    def kind_id(self) -> int:
-        return KINDS.index(self.kind)
-
-    FIELDS = ("kind", "lr", "beta1", "beta2", "tau")
-
-    def as_vector(self) -> torch.Tensor:
-        """(kind id, lr, beta1, beta2, tau) in fp64: what :meth:`FedAvg.resync` compares across clients."""
-        return torch.tensor([self.kind_id, self.lr, self.beta1, self.beta2, self.tau], dtype=torch.float64)
 
 
 def reference_step(x: torch.Tensor, anchor: torch.Tensor, m: torch.Tensor, v: Optional[torch.Tensor], n_opt: int,
@@ -95,23 +90,23 @@ def reference_step(x: torch.Tensor, anchor: torch.Tensor, m: torch.Tensor, v: Op
     return xo, xo.clone(), mo, vo
 
 
-class ServerOpt:
+class ServerOpt(ReplicatedState):
     """Replicated server optimizer state of one client: ``anchor`` (the previous global model), ``m``, ``v``."""
 
     def __init__(self, trainer, cfg: ServerOptConfig):
         x = trainer.float_state()
-        self.cfg = cfg
+        super().__init__(x, cfg)
         self.n = x.numel()
         self.n_opt = int(trainer.n_params())
         if not 0 <= self.n_opt <= self.n:
             raise ValueError(f"n_params() = {self.n_opt} outside the float state of {self.n} entries")
-        self.dev = x.device
         self.anchor = x.detach().clone()
         self.m = torch.zeros_like(self.anchor)
         self.v = torch.full_like(self.anchor, cfg.tau * cfg.tau)
-        self._nat = native.require() if x.is_cuda else None
-        self._snap = None
         self.steps = 0
+
+    def _rolled(self) -> List[torch.Tensor]:
+        return [self.anchor, self.m, self.v]
 
     def step(self, trainer) -> None:
         """``float_state()`` holds the aggregated mean on entry and the new global model on return."""
@@ -140,34 +135,9 @@ class ServerOpt:
         """The model was replaced from outside (resync, load): it is the new anchor; ``m`` and ``v`` are kept."""
         self.anchor.copy_(trainer.float_state())
 
-    def snapshot(self) -> None:
-        """Device copy of the three tensors (the client agent takes it at the start of every round)."""
-        if self._snap is None:
-            self._snap = tuple(torch.empty_like(t) for t in (self.anchor, self.m, self.v))
-        for d, s in zip(self._snap, (self.anchor, self.m, self.v)):
-            d.copy_(s, non_blocking=True)
-
-    def rollback(self) -> None:
-        """Back to the last :meth:`snapshot`, bit for bit (a void round must not leave a trace in the state)."""
-        if self._snap is None:
-            raise RuntimeError("ServerOpt.rollback() without a snapshot()")
-        for d, s in zip((self.anchor, self.m, self.v), self._snap):
-            d.copy_(s)
-
     def state_tensors(self) -> List[torch.Tensor]:
         """What a joining client must receive from the survivors (the anchor is the model itself)."""
         return [self.m, self.v]
-
-    def check_config(self, other: torch.Tensor, src: int) -> None:
-        """Raise if rank ``src``'s configuration (:meth:`ServerOptConfig.as_vector`) differs from the local one."""
-        mine = self.cfg.as_vector()
-        other = other.detach().cpu().to(torch.float64)
-        for i, name in enumerate(ServerOptConfig.FIELDS):
-            if float(mine[i]) != float(other[i]):
-                show = (lambda t: KINDS[int(t)] if 0 <= int(t) < len(KINDS) else int(t)) if i == 0 else float
-                raise RuntimeError(f"server optimizer configuration differs from rank {src}'s in {name!r}: "
-                                   f"local {show(mine[i])}, rank {src} {show(other[i])} -- every client must run "
-                                   "the same --server-opt settings, or the replicated state drifts apart")
 
 
 def add_server_opt_flags(ap) -> None:

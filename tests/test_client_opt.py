@@ -11,6 +11,7 @@ import torch.multiprocessing as mp
 from fedmi.parallel.client_opt import (KINDS, ClientOpt, ClientOptConfig, make_client_opt, reference_begin,
                                        reference_drift, reference_finish)
 from fedmi.parallel.fedavg import FedAvg
+from fedmi.parallel.server_opt import make_server_opt
 from tests.client_opt_check import (check_begin, check_fedprox, check_finish, check_scaffold_drift, draw_inputs)
 from tests.helpers import free_port, small_trainer
 
@@ -301,6 +302,15 @@ def test_finish_round_without_a_step_raises():
 
 
 # ---- 3. two gloo ranks -------------------------------------------------------------------------------------------------
+def _both(rank: int, start=None, tau: float = 1e-3, mu: float = 0.01):
+    """A stub trainer with ``rank``'s gradients (and ``_Stub(start)``'s model) and one FedAvg with fedadam and
+    scaffold attached."""
+    t = _Stub(rank)
+    if start is not None:
+        t.flat.copy_(_Stub(start).flat)
+    return t, FedAvg(server_opt=make_server_opt("fedadam", t, tau=tau), client_opt=make_client_opt("scaffold", t, mu))
+
+
 def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -343,6 +353,37 @@ def _worker(rank, world, port, q):
     except RuntimeError as e:
         out["mismatch"] = str(e)
     out["rs_anchor_ok"] = bool(torch.equal(fa3.client_opt.anchor, t3.flat[:t3.n_opt])) if rank == 0 else True
+    # both optimizers on one FedAvg: two rounds together, then rank 1 is replaced by a fresh client with another model
+    t4, fa4 = _both(rank, start=0)
+    for _ in range(2):
+        t4.train_epoch()
+        fa4.average(t4)
+    out.update(both_m=fa4.server_opt.m.clone(), both_v=fa4.server_opt.v.clone(), both_c=fa4.client_opt.c.clone())
+    if rank == 1:
+        t4, fa4 = _both(5)
+    fa4.resync(t4, 0)
+    out.update(both_rs_m=fa4.server_opt.m.clone(), both_rs_v=fa4.server_opt.v.clone(),
+               both_rs_c=fa4.client_opt.c.clone(), both_rs_x=t4.flat.clone(),
+               both_rs_anchor=fa4.server_opt.anchor.clone())
+    # a mismatch in either configuration.  Rank 0 cannot know and goes on to send what follows the compared
+    # vector: rank 1 receives it into scratch so that rank 0's resync completes.
+    for key, kw in (("both_bad_server", dict(tau=1e-3 if rank == 0 else 1e-2)),
+                    ("both_bad_client", dict(mu=0.01 if rank == 0 else 0.5))):
+        t5, fa5 = _both(rank, **kw)
+        try:
+            fa5.resync(t5, 0)
+            out[key] = ""
+        except RuntimeError as e:
+            out[key] = str(e)
+            # in FedAvg._hand_over's order: the state of the optimizer whose vector differed, then every later
+            # optimizer's vector and state
+            opts = fa5.opts()
+            bad = next(i for i, o in enumerate(opts) if o.cfg.FLAG in str(e))
+            rest = opts[bad].state_tensors()
+            for o in opts[bad + 1:]:
+                rest = rest + [o.cfg.as_vector()] + o.state_tensors()
+            for t in rest:
+                dist.broadcast(torch.empty_like(t), src=0)
     # tensors travel by value (numpy pickles): torch's fd-sharing reducer races the worker's exit
     q.put((rank, {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in out.items()}))
     dist.destroy_process_group()
@@ -413,7 +454,52 @@ def test_gloo_resync_rejects_other_settings(two_ranks):
     assert "'mu'" in msg and "0.5" in msg and "rank 0" in msg
 
 
+@pytest.mark.slow
+def test_gloo_resync_with_both_optimizers_hands_over_m_v_and_c(two_ranks):
+    r0, r1 = two_ranks[0], two_ranks[1]
+    for key in ("m", "v", "c"):
+        trained = r0[f"both_{key}"]
+        assert torch.equal(r1[f"both_{key}"], trained) and trained.max() > trained.min()    # replicated, not initial
+        assert torch.equal(r1[f"both_rs_{key}"], trained) and torch.equal(r0[f"both_rs_{key}"], trained)
+    assert torch.equal(r1["both_rs_x"], r0["both_rs_x"])
+    for r in (r0, r1):
+        assert torch.equal(r["both_rs_anchor"], r["both_rs_x"])
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("key,flag,name", [("both_bad_server", "--server-opt", "'tau'"),
+                                           ("both_bad_client", "--client-opt", "'mu'")])
+def test_gloo_resync_with_both_optimizers_names_the_flag_that_differs(two_ranks, key, flag, name):
+    assert two_ranks[0][key] == ""
+    msg = two_ranks[1][key]
+    assert flag in msg and name in msg and "rank 0" in msg
+    assert ("--client-opt" if flag == "--server-opt" else "--server-opt") not in msg
+
+
 # ---- 4. rollback ---------------------------------------------------------------------------------------------------------
+def test_both_optimizers_snapshot_average_rollback_bitwise():
+    """snapshot_opts() -> average() -> rollback_opts() at world 1: anchor, m, v and c, ci, corr come back bit for
+    bit, and the void round's gradient sum is dropped."""
+    t, fa = _both(0)
+    t.train_epoch()
+    fa.average(t)                                              # non-trivial m, v and c / ci / corr
+    rolled = [s for o in fa.opts() for s in o._rolled()]
+    assert [id(o) for o in fa.opts()] == [id(fa.server_opt), id(fa.client_opt)] and len(rolled) == 6
+    fa.snapshot_opts()
+    before = [s.clone() for s in rolled]
+    t.train_epoch()
+    fa.average(t)
+    assert all(not torch.equal(a, b) for a, b in zip(rolled, before))
+    t.train_epoch()                                            # the void round got as far as summing gradients
+    assert fa.client_opt.acc.any() and fa.client_opt.K == t.steps
+    fa.rollback_opts()
+    for got, want in zip(rolled, before):
+        assert torch.equal(got, want)
+    assert fa.client_opt.K == 0 and not fa.client_opt.acc.any()
+    fa.reset_opts(t)
+    assert torch.equal(fa.server_opt.anchor, t.flat)
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_snapshot_train_rollback_bitwise(kind):
     t = _Stub()

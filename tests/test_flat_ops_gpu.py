@@ -17,7 +17,7 @@ def S():
     return native.stream_handle()
 
 
-@pytest.mark.parametrize("n", [1, 7, 4096, 100003])
+@pytest.mark.parametrize("n", [1, 7, 1027, 4096, 100003, 2048 * 256 * 4 + 5])   # 1027: vectors plus tail; the last: past the grid cap
 def test_sgd_flat(nat, gpu_device, n):
     torch.manual_seed(n)
     p = torch.randn(n, device=gpu_device)
