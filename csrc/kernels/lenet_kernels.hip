@@ -442,45 +442,85 @@ FEDMI_DEV BwdLds bwd_lds(unsigned char* scratch, const uint8_t* raw, const bf16*
   return L;
 }
 
-// zero the out-grad images, the shifted copies' tails (x' + s beyond the row) and the bias sums
+// zero the out-grad images (scattered into sparsely: cleared whole), the bias sums, and of the shifted
+// copies only what a consumer reads and the builders below do not write:
+//   xsh   conv1 wgrad reads columns 0..31 of rows 0..31 of every (shift, c < 3) plane -- never the row
+//         pad 32..39, the 72-element plane pad or the 48-element copy pad.  The builder writes columns
+//         0..31-s of copy s (odd copies: also a zero at 32-s), so the unwritten part that is read lies in the
+//         tail 32-s..31 of copies 1..4.  It meets dY1 columns j >= 28, which are zero, but 0 x stale
+//         bits may be NaN: columns 28..31 of
+//         every row of copies 1..4 are cleared (8 B each; the builder rewrites 28..31-s afterwards).
+//   p1sh  conv2 wgrad reads all 16 columns of all 14 rows of every (shift, c) plane; the builder writes
+//         columns 0..13-s.  The unwritten 14-s..15 meet dY2w columns j >= 10, which are zero: columns
+//         8..15 of every row are cleared (16 B each; the builder rewrites 8..13-s afterwards).
+// Both builders run behind a later barrier, so the clears never race them.
 FEDMI_DEV void bwd_zero(const BwdLds& L) {
   zero_lds<NT_CONV>(L.dY2w, BW_DY2W * 2);
   zero_lds<NT_CONV>(L.dY2c, BW_DY2C * 2);
   zero_lds<NT_CONV>(L.dY1, BW_DY1 * 2);
-  zero_lds<NT_CONV>(L.xsh, BW_XSH * 2);
-  zero_lds<NT_CONV>(L.p1sh, BW_P1SH * 2);
-  if (threadIdx.x < 64) L.db[threadIdx.x] = 0.f;
+  const int tid = threadIdx.x;
+  if (tid < 512) {                                   // (copy 1..4, c slot of 4, y)
+    const int sh = 1 + (tid >> 7), c = (tid >> 5) & 3, y = tid & 31;
+    if (c < 3) *reinterpret_cast<uint2*>(L.xsh + sh * BW_XS_S + c * BW_XS_C + y * BW_XROW + 28) = make_uint2(0, 0);
+  } else if (tid < 512 + BW_P1SH / 16) {             // one 16-column row each
+    *reinterpret_cast<uint4*>(L.p1sh + (tid - 512) * 16 + 8) = make_uint4(0, 0, 0, 0);
+  }
+  if (tid < 64) L.db[tid] = 0.f;
 }
+static_assert((BW_XS_S * 2) % 8 == 0 && (BW_XS_C * 2) % 8 == 0 && (BW_XROW * 2) % 8 == 0 && BW_O_P1SH % 16 == 0,
+              "tail clears are aligned 8 / 16-byte stores");
+static_assert(512 + BW_P1SH / 16 <= NT_CONV, "one tail clear per thread");
 
-// each augmented pixel / pooled value is computed once and stored into its 5
-// column-shifted copies: copy s holds element x at column x - s
-FEDMI_DEV void bwd_build_shifted_img(const BwdLds& L, const Aug& a, int tid, int nthr) {
-  for (int e = tid; e < IMG_BYTES; e += nthr) {
-    const int c = e >> 10, y = (e >> 5) & 31, x = e & 31;
-    const bf16 v = (bf16)aug_pixel(L.raw, a, c, y, x);
-    bf16* row = L.xsh + c * BW_XS_C + y * BW_XROW + x;
+// The 5 column-shifted copies (copy s holds element x at column x - s) are stored as aligned 4-byte pairs:
+// a thread holds the row elements x, x + 1, x + 2 (x even; zero past the row's end) as p01 = (x, x + 1) and
+// p12 = (x + 1, x + 2).  An even shift puts (x, x + 1) at the even column x - s, an odd shift puts
+// (x + 1, x + 2) at the even column x + 1 - s -- half the LDS stores of element-wise copies.  The zero
+// past the row's end lands in the tail of the odd copies.  row: copy 0, column x.
+FEDMI_DEV void store_shifted_pairs(bf16* row, int copy_stride, int x, unsigned p01, unsigned p12) {
 #pragma unroll
-    for (int sh = 0; sh < 5; ++sh)
-      if (x >= sh) row[sh * BW_XS_S - sh] = v;
+  for (int sh = 0; sh < 5; ++sh) {
+    if (sh & 1) {
+      if (x + 1 >= sh) *reinterpret_cast<unsigned*>(row + sh * copy_stride + 1 - sh) = p12;
+    } else {
+      if (x >= sh) *reinterpret_cast<unsigned*>(row + sh * copy_stride - sh) = p01;
+    }
   }
 }
+FEDMI_DEV unsigned pack2(bf16 lo, bf16 hi) {
+  return (unsigned)__builtin_bit_cast(unsigned short, lo) | ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
+}
+// from the forward's channels-last image xcl [36][40][4] (the augmented pixels: one decode per pixel in the
+// whole kernel); its column 32 is zero.  item = (c, y, pair of columns)
+FEDMI_DEV void bwd_build_shifted_img(const BwdLds& L, const bf16* xcl, int tid, int nthr) {
+  for (int e = tid; e < 3 * IMG * (IMG / 2); e += nthr) {
+    const int c = e >> 9, y = (e >> 4) & 31, x = 2 * (e & 15);
+    const bf16* px = xcl + (y * 40 + x) * 4 + c;
+    const bf16 v0 = px[0], v1 = px[4], v2 = px[8];
+    store_shifted_pairs(L.xsh + c * BW_XS_C + y * BW_XROW + x, BW_XS_S, x, pack2(v0, v1), pack2(v1, v2));
+  }
+}
+// from pool1 CHW (index = plane row * 14 + x: no division).  item = (plane row c * 14 + y, pair of columns)
 FEDMI_DEV void bwd_build_shifted_p1(const BwdLds& L, int tid, int nthr) {
-  for (int e = tid; e < NP1; e += nthr) {
-    const int c = e / 196, rem = e - c * 196, y = rem / P1, x = rem - y * P1;
-    const bf16 v = L.p1r[e];
-    bf16* row = L.p1sh + (c * 14 + y) * 16 + x;
-#pragma unroll
-    for (int sh = 0; sh < 5; ++sh)
-      if (x >= sh) row[sh * (6 * 14 * 16) - sh] = v;
+  for (int e = tid; e < C1 * P1 * 8; e += nthr) {
+    const int rw = e >> 3, x = 2 * (e & 7);
+    if (x >= P1) continue;
+    const bf16* pv = L.p1r + rw * P1 + x;
+    const bf16 v0 = pv[0], v1 = pv[1], v2 = x + 2 < P1 ? pv[2] : (bf16)0.f;
+    store_shifted_pairs(L.p1sh + rw * 16 + x, 6 * 14 * 16, x, pack2(v0, v1), pack2(v1, v2));
   }
 }
+static_assert(BW_XS_S % 2 == 0 && BW_XS_C % 2 == 0 && BW_XROW % 2 == 0 && BW_O_P1SH % 4 == 0, "pair stores are 4-byte aligned");
 
 // d(pool2) -> conv2 out-grad images + conv2 bias sums, then conv2 wgrad + dgrad, conv1 wgrad,
 // and the sample's gradient slab.  Stamps slots 2..5 of kernel 'sk'.  db: [0, 16) conv2 bias,
 // [16, 58) conv1 bias partials of the 7 dgrad waves (combined in wave order: no LDS float atomics).
 FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int stamp_wg) {
   (void)sk; (void)stamp_wg;
-  const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+  // the lane id passes through an empty asm so that the lane-derived indices below are recomputed here (a few
+  // VALU ops) instead of being held from the kernel's start across the FC chain: see the note in the CE block
+  int lane = lane_id();
+  asm volatile("" : "+v"(lane));
+  const int tid = threadIdx.x, wave = wave_id();
   const int kq = (lane >> 4) * 8, n16 = lane & 15, rq = (lane >> 4) * 4;
   float* db = L.db;
   // thread = (channel o, slot r < 32): the 25 positions of a channel sit in 32 consecutive lanes, so
@@ -527,14 +567,14 @@ FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int s
 
   // ---- conv2 dgrad: dP1[c][pos] = sum_(r,s,o) dY2[o][y-r][x-s] W2[o][c][r][s]
   //      M = 196 positions (13 tiles), N = 6 (pad 16), K = 416 (13 steps)
-  int koff[13];   // per-lane K-group offsets into dY2c relative to the output position
-#pragma unroll
-  for (int ks = 0; ks < 13; ++ks) {
-    const int G = ks * 4 + (lane >> 4), g = G >> 1;
-    const int r = g / 5, sc = g - r * 5;
-    koff[ks] = g < 25 ? (-r * 18 - sc) * BW_DY2S + (G & 1) * 8 : 0;   // pad group: weight 0, any in-bounds read
-  }
   if (wave < 7) {
+    int koff[13];   // per-lane K-group offsets into dY2c relative to the output position
+#pragma unroll
+    for (int ks = 0; ks < 13; ++ks) {
+      const int G = ks * 4 + (lane >> 4), g = G >> 1;
+      const int r = g / 5, sc = g - r * 5;
+      koff[ks] = g < 25 ? (-r * 18 - sc) * BW_DY2S + (G & 1) * 8 : 0;   // pad group: weight 0, any in-bounds read
+    }
     const int ta = 2 * wave, tb = 2 * wave + 1;          // tb == 13 (wave 6) is a duplicate, not stored
     int pa = ta * 16 + n16, pb = tb * 16 + n16;
     if (pa >= 196) pa = 0;
@@ -556,14 +596,20 @@ FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int s
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int t = h ? tb : ta;
+        // the lane's 4 consecutive positions: all below 196 or none (196 = 4 * 49), so their pooled values and
+        // argmax codes are one aligned 8-byte and one 4-byte read, and (y, x) one division, then stepped
+        const int p0 = t * 16 + rq;
+        if (p0 < 196) {
+          const int py0 = p0 / P1, px0 = p0 - py0 * P1;
+          const uint2 pv = *reinterpret_cast<const uint2*>(L.p1r + c * 196 + p0);
+          const unsigned av = *reinterpret_cast<const unsigned*>(L.am1s + c * 196 + p0);
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const int p = t * 16 + rq + rr;
-          if (p < 196) {
-            const int py = p / P1, px = p - py * P1;
-            const float pooled = (float)L.p1r[c * 196 + p];
+          for (int rr = 0; rr < 4; ++rr) {
+            const int wrap = px0 + rr >= P1, py = py0 + wrap, px = px0 + rr - wrap * P1;
+            const unsigned w = rr < 2 ? pv.x : pv.y;
+            const float pooled = __builtin_bit_cast(float, (rr & 1) ? (w & 0xffff0000u) : (w << 16));
             const float g = pooled > 0.f ? acc[h][rr] : 0.f;
-            const int am = L.am1s[c * 196 + p];
+            const int am = (av >> (8 * rr)) & 3;
             const int yy = 2 * py + (am >> 1), xx = 2 * px + (am & 1);
             L.dY1[c * BW_DY1S + yy * 32 + xx] = (bf16)g;
             csum += g;
@@ -614,9 +660,10 @@ FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int s
   }
   __syncthreads();
   FEDMI_STAMP(sk, 4);
-  for (int e = tid; e < C1 * 75; e += NT_CONV) {
-    const int o = e / 75, kk = e - o * 75;
-    slab[P_C1W + e] = L.w1part[o * 80 + kk] + L.w1part[(6 + o) * 80 + kk] + L.w1part[(12 + o) * 80 + kk];
+  if (tid < C1 * 128) {                                   // thread = (o, slot of 128): no division
+    const int o = tid >> 7, kk = tid & 127;
+    if (kk < 75)
+      slab[P_C1W + o * 75 + kk] = L.w1part[o * 80 + kk] + L.w1part[(6 + o) * 80 + kk] + L.w1part[(12 + o) * 80 + kk];
   }
   if (tid < C1) {
     float b = 0.f;
@@ -660,8 +707,10 @@ constexpr int AUX_CORR = AUX_LOSS + MAX_TRAIN_BATCH * 4;          // f32 [128]
 constexpr int AUX_BYTES = AUX_CORR + MAX_TRAIN_BATCH * 4;
 static_assert(AUX_BYTES <= MAX_TRAIN_BATCH * F0 * 4, "FC side buffers must fit in dact2");
 
-// KS1 LDS (bytes): persistent operands, then one scratch region shared by the forward
-// (x image, conv1 out, pool1 channels-last, conv2 out) and the backward (BwdLds scratch).
+// KS1 LDS (bytes): persistent operands, then the backward's scratch (BwdLds), then the fc1 partials region,
+// whose idle time up to dX also hosts the forward's two images (x and pool1, channels-last).  Nothing of the
+// forward aliases the backward's scratch, so that is cleared while the stage loads are in flight and the
+// shifted copies are built during the conv2 phase (the image's by the waves conv2 leaves idle).
 constexpr int S_O_RAW = 0, S_O_P1R = 3072, S_O_AM1 = S_O_P1R + 2368, S_O_AM2 = S_O_AM1 + 1184,
               S_O_X = S_O_AM2 + 416, S_O_DX = S_O_X + F0P * 2, S_O_WDG = S_O_DX + F0 * 4,
               S_O_FC = S_O_WDG + 16 * BW_WDGS * 2, S_O_W1C = S_O_FC + 2048, S_O_W2C = S_O_W1C + 16 * 136 * 2,
@@ -670,17 +719,22 @@ constexpr int S_O_RAW = 0, S_O_P1R = 3072, S_O_AM1 = S_O_P1R + 2368, S_O_AM2 = S
 // fragment read land on distinct bank groups).  Staged ONCE per workgroup: per-wave register loads of
 // the same fragments cost 16 waves x 11 KB of L2 traffic per sample.
 constexpr int S_W1C_LD = 136, S_W2C_LD = 232;
-constexpr int S_F_XCL = 0, S_F_C1 = S_F_XCL + 36 * 40 * 4 * 2, S_F_P1 = S_F_C1 + NPOS1 * 8 * 4,
-              S_F_C2 = S_F_P1 + 14 * 14 * 8 * 2, S_F_END = S_F_C2 + C2 * NPOS2 * 4;
-// fc1 cross-wave partials: [128 n][4 rows] for the forward, [16 waves][F0P] for dX (one region, two uses)
-constexpr int S_O_RED = S_O_SCR + (S_F_END > BW_SCRATCH ? S_F_END : BW_SCRATCH);
+// fc1 cross-wave partials: [128 n][4 rows] for the forward, [16 waves][F0P] for dX (one region, two uses);
+// behind the forward partials: x channels-last [36][40][4] bf16 (stage .. conv2 phase) and pool1
+// channels-last [14][14][8] bf16 (conv1 .. conv2), both dead long before dX
+constexpr int S_O_RED = S_O_SCR + BW_SCRATCH;
+constexpr int S_R_XCL = 128 * 4 * 4, S_R_P1 = S_R_XCL + 36 * 40 * 4 * 2, S_R_END = S_R_P1 + 14 * 14 * 8 * 2;
+static_assert(S_R_END <= NW_CONV * F0P * 4 && S_O_RED % 16 == 0, "forward images fit behind the fc1 partials");
 constexpr int S_O_W3 = S_O_RED + NW_CONV * F0P * 4;    // fc3 image [16 n][96 f] bf16, staged with the conv weights
 constexpr int S_END = S_O_W3 + 16 * 96 * 2;
 static_assert(S_END <= 160 * 1024, "KS1 LDS");
+static_assert(S_O_P1R % 8 == 0 && S_O_AM1 % 4 == 0, "pool1 backward reads 4 positions per access");
 // FC scratch (floats, bf16-rounded values where the old MFMA path used bf16 operands)
 constexpr int SF_H1 = 0, SF_H2 = 128, SF_Z = 224, SF_DZ3 = 240, SF_DZ2 = 256, SF_DZ1 = 352, SF_END = 480;
 static_assert(SF_END * 4 <= 2048, "FC scratch");
 
+// bf16 products are exact in fp32 and are added one by one in element order: this order is part of the step's
+// bit-exact result (v_dot2c_f32_bf16 sums a pair differently in rare cases and is not used for that reason)
 FEDMI_DEV float dot8(const bf16x8& a, const bf16x8& b, float acc) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc += (float)a[j] * (float)b[j];
@@ -735,11 +789,9 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
   bf16* wdg = reinterpret_cast<bf16*>(smem + S_O_WDG);
   float* fcs = reinterpret_cast<float*>(smem + S_O_FC);
   float* red = reinterpret_cast<float*>(smem + S_O_RED);
-  unsigned char* scr = smem + S_O_SCR;
-  bf16* xcl = reinterpret_cast<bf16*>(scr + S_F_XCL);
-  float* c1 = reinterpret_cast<float*>(scr + S_F_C1);
-  bf16* p1cl = reinterpret_cast<bf16*>(scr + S_F_P1);
-  float* c2 = reinterpret_cast<float*>(scr + S_F_C2);
+  bf16* xcl = reinterpret_cast<bf16*>(smem + S_O_RED + S_R_XCL);
+  bf16* p1cl = reinterpret_cast<bf16*>(smem + S_O_RED + S_R_P1);
+  const BwdLds L = bwd_lds(smem + S_O_SCR, raw, p1r, am1s, am2s, dxs, wdg);
   FEDMI_STAMP(0, 0);
 
   // ---- stage: image (192 x 16 B) and the conv2 dgrad weight image (832 x 16 B) -- one
@@ -779,6 +831,7 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
     bias2 = params[P_C2B + n16];
     a = aug_params(augment, seed, round_ctr, gidx);
     zero_lds<NT_CONV>(xcl, 36 * 40 * 4 * 2);
+    bwd_zero(L);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int e = tid + u * NT_CONV;
@@ -798,16 +851,11 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
       }
     }
   }
-  int go1[4], go2[7];
+  int go1[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
     const int g = ks * 4 + (lane >> 4);
     go1[ks] = g < 15 ? ((g / 3) * 40 + 2 * (g % 3)) * 4 : 0;
-  }
-#pragma unroll
-  for (int ks = 0; ks < 7; ++ks) {
-    const int g = ks * 4 + (lane >> 4);
-    go2[ks] = g < 25 ? ((g / 5) * P1 + (g % 5)) * 8 : 0;
   }
   __syncthreads();
   FEDMI_STAMP(1, 7);
@@ -890,6 +938,12 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
     const int y = 2 * (q / P2) + ((n16 >> 1) & 1), x = 2 * (q % P2) + (n16 & 1);
     const bf16* pb = p1cl + (y * P1 + x) * 8;
     const bf16* wb = w2c + n16 * S_W2C_LD + kq;
+    int go2[7];   // computed here, not at the kernel's start: 7 registers less across conv1 (the kernel sits at the 128-VGPR cap)
+#pragma unroll
+    for (int ks = 0; ks < 7; ++ks) {
+      const int g = ks * 4 + (lane >> 4);
+      go2[ks] = g < 25 ? ((g / 5) * P1 + (g % 5)) * 8 : 0;
+    }
     f32x4 acc = zero4();
 #pragma unroll
     for (int ks = 0; ks < 7; ++ks) acc = mfma16(ld8(pb + go2[ks]), ld8(wb + ks * 32), acc);
@@ -906,10 +960,16 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
       xrow[e] = mb;
       act2T[(size_t)e * MAX_TRAIN_BATCH + s] = mb;
     }
-  } else if (tid >= 7 * 64 && tid < 7 * 64 + (F0P - F0)) {     // act2 row padding 400..415
-    const int e = F0 + tid - 7 * 64;
-    xrow[e] = (bf16)0.f;
-    act2T[(size_t)e * MAX_TRAIN_BATCH + s] = (bf16)0.f;
+    bwd_build_shifted_p1(L, tid, 7 * 64);   // the shorter of the two builders rides behind conv2
+  } else {
+    // waves 7..15: the act2 row padding 400..415, then the conv backward's column-shifted copies of the
+    // image (final since the augmentation's barrier; pool1's copies: waves 0..6 above)
+    if (tid < 7 * 64 + (F0P - F0)) {
+      const int e = F0 + tid - 7 * 64;
+      xrow[e] = (bf16)0.f;
+      act2T[(size_t)e * MAX_TRAIN_BATCH + s] = (bf16)0.f;
+    }
+    bwd_build_shifted_img(L, xcl, tid - 7 * 64, NT_CONV - 7 * 64);
   }
   FEDMI_STAMP(0, 4);
   // fc2 weight chunks and the FC biases (fc3's 3 KB image is in LDS since the stage)
@@ -922,8 +982,6 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
   const float fb2 = params[P_F2B + min(fn, F2 - 1)];
   const float fb3 = params[P_F3B + min(fn, NCLS - 1)];
   __syncthreads();
-  const BwdLds L = bwd_lds(scr, raw, p1r, am1s, am2s, dxs, wdg);
-  bwd_zero(L);                 // the forward scratch is dead: the backward's images take its place
   FEDMI_STAMP(0, 5);
 
   // ---- fc1: h1[n] = relu(x . W1[n] + b1)  (thread = (n, 8-lane k slice))
@@ -965,8 +1023,7 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
   }
   __syncthreads();
   FEDMI_STAMP(1, 1);
-  // ---- fc3: logits (waves 0..1); waves 2..15 meanwhile build the conv backward's column-shifted
-  //      copies (zeroed after pool2): the FC chain's idle waves absorb that LDS work
+  // ---- fc3: logits (waves 0..1)
   if (fn < 16) {
     float acc = 0.f;
 #pragma unroll
@@ -974,15 +1031,18 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
       if (fq * 8 + 64 * i < 96) acc = dot8f(fcs + SF_H2 + fq * 8 + 64 * i, ld8(w3s + fn * 96 + fq * 8 + 64 * i), acc);
     acc = sum8lanes(acc);
     if (fq == 0) fcs[SF_Z + fn] = fn < NCLS ? acc + fb3 : 0.f;
-  } else {
-    bwd_build_shifted_img(L, a, tid - 128, NT_CONV - 128);
   }
   __syncthreads();
   FEDMI_STAMP(1, 2);
   // ---- cross-entropy (mean over the batch nb), accuracy, dZ3: lanes 0..15 of wave 0 hold one
-  //      class each (max / sum by xor shuffles); waves 1..15 build the pool1 shifted copies
+  //      class each (max / sum by xor shuffles)
   if (wave == 0) {
-    const int n = lane & 15;
+    // the lane id passes through an empty asm so that n is recomputed here (one VALU op): KS1 sits at the
+    // 128-VGPR cap, and n16 * 4 held from the kernel's start for this block was spilled to scratch -- a launch
+    // that uses scratch also slows the launch behind it (KS2) by about 1 us
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const int n = ln & 15;
     const float zn = n < NCLS ? fcs[SF_Z + n] : -INFINITY;
     float mx = zn;
 #pragma unroll
@@ -1007,8 +1067,6 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
       reinterpret_cast<float*>(auxp + AUX_LOSS)[s] = lse - zy;
       reinterpret_cast<float*>(auxp + AUX_CORR)[s] = ((int)cand == y) ? 1.f : 0.f;
     }
-  } else {
-    bwd_build_shifted_p1(L, tid - 64, NT_CONV - 64);
   }
   __syncthreads();
   FEDMI_STAMP(1, 3);
@@ -1153,9 +1211,14 @@ FEDMI_DEV f32x4 batch_tile(const bf16* __restrict__ a, const bf16* __restrict__ 
     m[r] = mom[idx[r] >= 0 ? idx[r] : 0];
   }
   f32x4 acc = zero4();
+  if (nb == MAX_TRAIN_BATCH) {   // workgroup-uniform: a full batch (all but an epoch's last step) has nothing to mask
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks)
-    acc = mfma16(mask_cols(av[ks], ks * 32 + kq, nb), mask_cols(bv[ks], ks * 32 + kq, nb), acc);
+    for (int ks = 0; ks < 4; ++ks) acc = mfma16(av[ks], bv[ks], acc);
+  } else {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+      acc = mfma16(mask_cols(av[ks], ks * 32 + kq, nb), mask_cols(bv[ks], ks * 32 + kq, nb), acc);
+  }
   return acc;
 }
 

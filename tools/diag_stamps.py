@@ -38,7 +38,7 @@ def main():
     if True:   # KS1 + KS2 (the only training path)
         # KS1: forward slots 0..6 under kernel 0, its backward slots 2..5 under kernel 2; KS2 under kernel 3
         ks1 = np.concatenate([st[0, :128, :7], st[2, :128, 2:6]], axis=1)
-        phases = ["stage+aug", "conv1", "pool1", "conv2", "pool2+zero+shift", "fc fwd+bwd", "dY2 scatter",
+        phases = ["stage+zero+aug", "conv1", "pool1", "conv2|shift build", "pool2 barrier", "fc fwd+bwd", "dY2 scatter",
                   "c2 wgrad+dgrad", "c1 wgrad", "slab store"]
         a = ks1[ks1[:, 0] > 0]
         d = np.diff(a, axis=1)
@@ -52,7 +52,7 @@ def main():
         k0 = k0[k0[:, 0] > 0]
         if len(f) and len(k0):
             print(f"    stage loads landed med {np.median(k0[:len(f), 0] * 0 + f[:, 7] - k0[:len(f), 0]):8.0f}")
-            fcn = ["fc1+h1T", "fc2", "fc3|shift build", "CE", "dH2", "dH1"]
+            fcn = ["fc1+h1T", "fc2", "fc3", "CE", "dH2", "dH1"]
             prev = k0[:len(f), 5]
             for j, nm in enumerate(fcn):
                 print(f"    fc.{nm:14s} med {np.median(f[:, j] - prev):8.0f}")
