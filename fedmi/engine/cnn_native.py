@@ -3,13 +3,20 @@
 * ResNet-18/34 (BasicBlock) and ResNet-50/101/152 (Bottleneck), src/models/resnet.py:14-124
 * MobileNet (depthwise-separable, the reference's default model), src/models/mobilenet.py:11-52
 * MobileNetV2 (inverted residuals), src/models/mobilenetv2.py:11-77
+* VGG-11/13/16/19 (conv+bias, BN, ReLU, 2x2 max pools), src/models/vgg.py:14-38
+* PreActResNet-18/34/50/101/152 (pre-activation blocks), src/models/preact_resnet.py:12-94
+* GoogLeNet (Inception modules), src/models/googlenet.py:7-98
 
 The zoo ``nn.Module`` is only the parameter/buffer container (its
 ``state_dict`` keeps the reference key names and lives in fedmi's flat fp32
 buffers); the training step is an explicit schedule of fedmi kernels on NHWC
-bf16 activations.  A network is a list of *blocks*; a block is a chain of
-*units* (conv or depthwise conv -> BatchNorm -> optional ReLU) whose last BN is
-fused with the block's shortcut (none / identity residual / projection
+bf16 activations.  Every family is a *plan* (``PLANS``): it owns its buffers and
+its ``forward`` / ``backward`` schedule and shares one skeleton, a chain of
+*units* (conv or depthwise conv -> BatchNorm -> optional ReLU; ``_chain_fwd`` /
+``_chain_bwd``).  What a plan adds is how chains join: the pre-activation
+shortcut fan-in (``_PreActPlan``), the Inception branch concat (``_GoogPlan``),
+or, for the first four families (``_BlockPlan``), a list of *blocks* whose last
+BN is fused with the block's shortcut (none / identity residual / projection
 conv+BN) and output ReLU in one ``bn_apply`` launch:
 
   forward   prep_input (crop/flip/normalize, device-side batch start)
@@ -52,6 +59,11 @@ BN_EPS = 1e-5
 BN_MOM = 0.1
 
 
+def _nhwc(t: torch.Tensor, nb: int, hw: int, c: int) -> torch.Tensor:
+    """The first ``nb`` images of a flat activation buffer as [nb, hw, hw, c]."""
+    return t[: nb * hw * hw * c].view(nb, hw, hw, c)
+
+
 class _Unit:
     """conv (dense or depthwise, no bias) + BatchNorm2d (+ ReLU), with its device buffers."""
 
@@ -85,10 +97,11 @@ class _Unit:
         self.smean = torch.empty(self.O, device=dev)
         self.sinv = torch.empty(self.O, device=dev)
         self.shift = torch.zeros(self.O, device=dev)   # previous batch mean: stats are sums of (z - shift)
+        self.zco = None     # [2][O] scale / shift stored by the forward BN (set by _BlockPlan: ReLU mask from z)
         self._fusable: Optional[bool] = None
 
     def view(self, t: torch.Tensor, nb: int) -> torch.Tensor:
-        return t[: nb * self.P * self.P * self.O].view(nb, self.P, self.P, self.O)
+        return _nhwc(t, nb, self.P, self.O)
 
     def bn_args(self, stats) -> dict:
         b = self.bn
@@ -163,6 +176,41 @@ class _Unit:
         return None if self.wd is None else (self.conv.weight.data, self.wd, self.stride, self.pad, self.C)
 
 
+# ---------------------------------------------------------------------------- the chain skeleton
+# Shared by every plan.  ``E`` is the engine (CNNNativeTrainer): its ``_bn`` / ``_bn_bwd`` / ``_wgrad`` /
+# ``_sums`` launch with the engine's accumulators and workspaces, ``E.wgrad_ws`` is the shared split-K workspace.
+def _chain_fwd(E, units: List[_Unit], h: torch.Tensor, nb: int, train: bool) -> torch.Tensor:
+    """conv -> BN(+ReLU) into ``y`` for ``units[:-1]``; returns the last unit's input.  The last unit is the
+    plan's: its BN is fused with whatever joins the chain there."""
+    for u in units[:-1]:
+        u.fwd(h, nb, u.stats if train else None, E.wgrad_ws)
+        h = E._bn(u, u.view(u.z, nb), u.view(u.y, nb), train, u.relu, co_out=u.zco if train else None)
+    return h
+
+
+def _chain_bwd(E, units: List[_Unit], nb: int, fuse: bool, dz: Optional[torch.Tensor] = None) -> None:
+    """wgrad(v), dgrad(v -> w.dy), bn_bwd(w) for (w, v) = (units[j - 1], units[j]), j from the last unit down
+    to 1.  ``dz``: the last unit's outgoing gradient (None: its own ``dz`` buffer).  The chain head units[0]
+    (its WGRAD, and where its input gradient goes) is the plan's.
+    ``fuse``: w's BN-backward sums are taken in the epilogue of v's DGRAD where that DGRAD can (``E._sums``)."""
+    for j in range(len(units) - 1, 0, -1):
+        v, w = units[j], units[j - 1]
+        wy, dwy = w.view(w.y, nb), w.view(w.dy, nb)
+        E._wgrad(v, wy, nb, dz=dz)
+        y, msc = wy if w.relu else None, None
+        bs = E._sums(v, w, nb, y) if fuse else None
+        if bs is not None and w.zco is not None:   # ReLU mask from z: y is not re-read
+            bs.update(y=None, msc=w.zco)
+            y, msc = None, w.zco
+        v.dgrad(nb, dwy, E.wgrad_ws, dz=dz, bn_sums=bs)
+        E._bn_bwd(w, nb, dwy, None, y, presummed=bs is not None, mask_bn=msc)
+        dz = None
+
+
+# ---------------------------------------------------------------------------- network plans
+# PLANS[type(model)](model, rows, dev, dt) -> a plan: units(), no_dgrad (the units that read the network
+# input: no data gradient), head_hw / head_c (the map handed to the head), forward(E, x, nb, train) -> that
+# map, backward(E, x, nb, dhead).
 class _Block:
     """Chain of units; the last unit's BN is fused with the shortcut and the output ReLU, optionally
     followed by MaxPool2d(2, 2) (VGG)."""
@@ -200,21 +248,88 @@ class _Block:
     def units(self) -> List[_Unit]:
         return self.main + ([self.proj] if self.proj else [])
 
-    def out_view(self, nb: int) -> torch.Tensor:
-        return self.out[: nb * self.out_hw * self.out_hw * self.cout].view(nb, self.out_hw, self.out_hw, self.cout)
 
-    def pre_view(self, nb: int) -> torch.Tensor:
-        return self.pre[: nb * self.pre_hw * self.pre_hw * self.cout].view(nb, self.pre_hw, self.pre_hw, self.cout)
+class _BlockPlan:
+    """ResNet, MobileNet, MobileNetV2, VGG: a list of blocks."""
 
-    def dpre_view(self, nb: int) -> torch.Tensor:
-        return self.dpre[: nb * self.pre_hw * self.pre_hw * self.cout].view(nb, self.pre_hw, self.pre_hw, self.cout)
+    def __init__(self, blocks: List[_Block], dev):
+        self.blocks = blocks
+        self.head_hw, self.head_c = blocks[-1].out_hw, blocks[-1].cout
+        self.no_dgrad = blocks[0].units() if blocks[0].first else []
+        # a ReLU'd BN inside a block (no residual) whose backward is chained: the forward stores its scale /
+        # shift, and the backward derives the ReLU mask from z (z * sc + sh > 0) instead of re-reading the
+        # materialised y
+        for b in blocks:
+            for v in b.main[:-1]:
+                if v.relu and cnn.bn_bwd_chain_floats(v.O):
+                    v.zco = torch.empty(2, v.O, device=dev)
 
-    def in_view(self, t: torch.Tensor, nb: int) -> torch.Tensor:
-        return t[: nb * self.in_hw * self.in_hw * self.cin].view(nb, self.in_hw, self.in_hw, self.cin)
+    def units(self) -> List[_Unit]:
+        return [u for b in self.blocks for u in b.units()]
+
+    def forward(self, E, x: torch.Tensor, nb: int, train: bool) -> torch.Tensor:
+        a = x
+        for b in self.blocks:
+            last = b.main[-1]
+            h = _chain_fwd(E, b.main, a, nb, train)
+            last.fwd(h, nb, last.stats if train else None, E.wgrad_ws)
+            out = _nhwc(b.pre, nb, b.pre_hw, b.cout)
+            z = last.view(last.z, nb)
+            if b.shortcut == "proj":
+                p = b.proj
+                p.fwd(a, nb, p.stats if train else None, E.wgrad_ws)
+                E._bn(last, z, out, train, b.out_relu, z2=p.view(p.z, nb), b=p.bn_args(p.stats))
+            elif b.shortcut == "identity":
+                E._bn(last, z, out, train, b.out_relu, res=a)
+            else:
+                E._bn(last, z, out, train, b.out_relu)
+            a = _nhwc(b.out, nb, b.out_hw, b.cout)
+            if b.pool:
+                cnn.maxpool2(out, out=a)
+        return a
+
+    def backward(self, E, x: torch.Tensor, nb: int, dhead: torch.Tensor) -> None:
+        dya, dyb, pres = dhead, None, False
+        ws = E.wgrad_ws
+        for i in range(len(self.blocks) - 1, -1, -1):
+            b = self.blocks[i]
+            prev = None if b.first else self.blocks[i - 1]
+            a_in = x if b.first else _nhwc(prev.out, nb, prev.out_hw, prev.cout)
+            pre = _nhwc(b.pre, nb, b.pre_hw, b.cout)
+            din_b = _nhwc(b.din_b, nb, b.in_hw, b.cin) if b.din_b is not None else None
+            if b.pool:   # grad wrt the pooled output -> grad wrt the pre-pool activation
+                dya = cnn.maxpool2_bwd(pre, dya, out=_nhwc(b.dpre, nb, b.pre_hw, b.cout))
+            # pres: the next block's first DGRAD wrote dya = (its grad + the shortcut grad) and this BN's sums
+            E._bn_bwd(b.main[-1], nb, dya, dyb, pre if b.out_relu else None, zb=b.proj,
+                      gout=din_b if b.shortcut == "identity" else None, presummed=pres)
+            _chain_bwd(E, b.main, nb, fuse=True)
+            # the chain head: the block input's grad, joined with the shortcut's
+            v = b.main[0]
+            E._wgrad(v, a_in, nb)
+            bs = None
+            if not b.first and not prev.pool:
+                ppre = _nhwc(prev.pre, nb, prev.pre_hw, prev.cout)
+                bs = E._sums(v, prev.main[-1], nb, ppre if prev.out_relu else None, zb=prev.proj,
+                             add=din_b is not None)
+            # fused: the shortcut's grad first, then conv1's DGRAD adds it and takes the previous block's
+            # BN-backward sums from the complete grad; else the previous block's bn_bwd takes both grads
+            if b.proj is not None and bs is not None:
+                E._wgrad(b.proj, a_in, nb)
+                b.proj.dgrad(nb, din_b, ws)
+            if not b.first:
+                din_a = _nhwc(b.din_a, nb, b.in_hw, b.cin)
+                if bs is not None:
+                    v.dgrad(nb, din_a, ws, add=din_b, bn_sums=bs)   # add=None: no shortcut
+                    dya, dyb, pres = din_a, None, True
+                else:
+                    v.dgrad(nb, din_a, ws)
+                    dya, dyb, pres = din_a, din_b, False
+            if b.proj is not None and bs is None:
+                E._wgrad(b.proj, a_in, nb)
+                b.proj.dgrad(nb, din_b, ws)
 
 
-# ---------------------------------------------------------------------------- network plans
-def _plan_resnet(m: ResNet, rows, dev, dt) -> List[_Block]:
+def _plan_resnet(m: ResNet, rows, dev, dt) -> _BlockPlan:
     blocks = [_Block([(m.conv1, m.bn1)], [True], 32, 8, rows, dev, first=True, act_dtype=dt)]
     hw, c = blocks[0].out_hw, blocks[0].cout
     for layer in (m.layer1, m.layer2, m.layer3, m.layer4):
@@ -231,10 +346,10 @@ def _plan_resnet(m: ResNet, rows, dev, dt) -> List[_Block]:
                        out_relu=True, act_dtype=dt)
             blocks.append(b)
             hw, c = b.out_hw, b.cout
-    return blocks
+    return _BlockPlan(blocks, dev)
 
 
-def _plan_mobilenet(m: MobileNet, rows, dev, dt) -> List[_Block]:
+def _plan_mobilenet(m: MobileNet, rows, dev, dt) -> _BlockPlan:
     blocks = [_Block([(m.conv1, m.bn1)], [True], 32, 8, rows, dev, first=True, act_dtype=dt)]
     hw, c = blocks[0].out_hw, blocks[0].cout
     for blk in m.layers:
@@ -243,10 +358,10 @@ def _plan_mobilenet(m: MobileNet, rows, dev, dt) -> List[_Block]:
                    act_dtype=dt)
         blocks.append(b)
         hw, c = b.out_hw, b.cout
-    return blocks
+    return _BlockPlan(blocks, dev)
 
 
-def _plan_mobilenetv2(m: MobileNetV2, rows, dev, dt) -> List[_Block]:
+def _plan_mobilenetv2(m: MobileNetV2, rows, dev, dt) -> _BlockPlan:
     blocks = [_Block([(m.conv1, m.bn1)], [True], 32, 8, rows, dev, first=True, act_dtype=dt)]
     hw, c = blocks[0].out_hw, blocks[0].cout
     for blk in m.layers:
@@ -263,10 +378,10 @@ def _plan_mobilenetv2(m: MobileNetV2, rows, dev, dt) -> List[_Block]:
         blocks.append(b)
         hw, c = b.out_hw, b.cout
     blocks.append(_Block([(m.conv2, m.bn2)], [True], hw, c, rows, dev, out_relu=True, act_dtype=dt))
-    return blocks
+    return _BlockPlan(blocks, dev)
 
 
-def _plan_vgg(m: VGG, rows, dev, dt) -> List[_Block]:
+def _plan_vgg(m: VGG, rows, dev, dt) -> _BlockPlan:
     """features = [Conv2d(bias), BN, ReLU | MaxPool2d(2)]..., AvgPool2d(1) (identity), classifier."""
     mods = list(m.features)
     blocks: List[_Block] = []
@@ -287,7 +402,7 @@ def _plan_vgg(m: VGG, rows, dev, dt) -> List[_Block]:
             i += 1
         else:
             raise TypeError(f"VGG plan: unexpected {type(mod).__name__}")
-    return blocks
+    return _BlockPlan(blocks, dev)
 
 
 class _PABlock:
@@ -321,11 +436,11 @@ class _PABlock:
     def all_units(self) -> List[_Unit]:
         return self.units + ([self.sc] if self.sc else [])
 
-    def in_view(self, t: torch.Tensor, nb: int) -> torch.Tensor:
-        return t[: nb * self.in_hw * self.in_hw * self.cin].view(nb, self.in_hw, self.in_hw, self.cin)
-
 
 class _PreActPlan:
+    """PreActResNet: stem conv, then pre-activation blocks; ``prev`` below is the unit whose BN is the current
+    block's bn1 (the stem, or the previous block's last unit)."""
+
     def __init__(self, m: PreActResNet, rows, dev, dt):
         blks = [b for layer in (m.layer1, m.layer2, m.layer3, m.layer4) for b in layer]
         # stem conv (no BN of its own) pairs with the first block's bn1
@@ -338,17 +453,54 @@ class _PreActPlan:
             pb = _PABlock(b, hw, c, rows, dev, dt, nb)
             self.blocks.append(pb)
             hw, c = pb.out_hw, pb.cout
+        self.head_hw, self.head_c = hw, c
+        self.no_dgrad = [self.stem]
 
     def units(self) -> List[_Unit]:
         return [self.stem] + [u for b in self.blocks for u in b.all_units()]
 
+    def forward(self, E, x: torch.Tensor, nb: int, train: bool) -> torch.Tensor:
+        ws = E.wgrad_ws
+        st = self.stem
+        st.fwd(x, nb, st.stats if train else None, ws)
+        E._bn(st, st.view(st.z, nb), st.view(st.y, nb), train, True)
+        prev = st
+        for b in self.blocks:
+            a = prev.view(prev.y, nb)                      # relu(bn1(x_b))
+            h = _chain_fwd(E, b.units, a, nb, train)
+            if b.sc is not None:
+                b.sc.fwd(a, nb, None, ws)
+                skip = b.sc.view(b.sc.z, nb)
+            else:
+                skip = prev.view(prev.z, nb)               # identity: x_b
+            L = b.units[-1]
+            L.fwd(h, nb, L.stats if (train and L.bn is not None) else None, ws, res=skip)
+            if L.bn is not None:
+                E._bn(L, L.view(L.z, nb), L.view(L.y, nb), train, True)
+            prev = L
+        return prev.view(prev.z, nb)
 
-def _plan_preact(m, rows, dev, dt):
-    return _PreActPlan(m, rows, dev, dt)
-
-
-def _nhwc(t: torch.Tensor, nb: int, hw: int, c: int) -> torch.Tensor:
-    return t[: nb * hw * hw * c].view(nb, hw, hw, c)
+    def backward(self, E, x: torch.Tensor, nb: int, dhead: torch.Tensor) -> None:
+        ws = E.wgrad_ws
+        g = dhead                                          # dL / d x_{b+1} (= dz of the block's last unit)
+        for bi in range(len(self.blocks) - 1, -1, -1):
+            b = self.blocks[bi]
+            prev = self.blocks[bi - 1].units[-1] if bi > 0 else self.stem
+            a = prev.view(prev.y, nb)
+            # the unfused BN backward (no sums in the DGRAD epilogues) is kept as found and is unmeasured
+            _chain_bwd(E, b.units, nb, fuse=False, dz=g)
+            u = b.units[0]
+            E._wgrad(u, a, nb)
+            u.dgrad(nb, prev.view(prev.dy, nb), ws)        # d a_b, conv1 branch
+            da2 = None
+            if b.sc is not None:                           # d a_b, shortcut-conv branch
+                E._wgrad(b.sc, a, nb, dz=g)
+                da2 = _nhwc(b.da2, nb, b.in_hw, b.cin)
+                b.sc.dgrad(nb, da2, ws, dz=g)
+            # bn1 of this block (prev's BN): dx_b = BN_bwd(relu mask) + identity-shortcut grad
+            E._bn_bwd(prev, nb, prev.view(prev.dy, nb), da2, a, dadd=None if b.sc is not None else g)
+            g = prev.view(prev.dz, nb)
+        E._wgrad(self.stem, x, nb)
 
 
 class _Incep:
@@ -393,15 +545,6 @@ class _Incep:
     def units(self) -> List[_Unit]:
         return [u for br in self.branches for u in br]
 
-    def out_view(self, t, nb):
-        return _nhwc(t, nb, self.hw, self.cout)
-
-    def in_view(self, t, nb):
-        return _nhwc(t, nb, self.hw, self.cin)
-
-    def final_view(self, t, nb):                             # the module's result (after the stage pool)
-        return _nhwc(t, nb, self.out_hw, self.cout)
-
     def slice(self, t4, k):
         return t4[..., self.offs[k]:self.offs[k] + self.widths[k]]
 
@@ -425,17 +568,66 @@ class _GoogPlan:
         if m.avgpool.kernel_size not in (hw, (hw, hw)):
             raise TypeError("GoogLeNet plan: the head must average the whole final map")
         self.head_hw, self.head_c = hw, c
+        self.no_dgrad = [self.pre]
 
     def units(self) -> List[_Unit]:
         return [self.pre] + [u for I in self.mods for u in I.units()]
 
+    def forward(self, E, x: torch.Tensor, nb: int, train: bool) -> torch.Tensor:
+        ws = E.wgrad_ws
+        p = self.pre
+        p.fwd(x, nb, p.stats if train else None, ws)
+        a = E._bn(p, p.view(p.z, nb), p.view(p.y, nb), train, True)
+        for I in self.mods:
+            out = _nhwc(I.out, nb, I.hw, I.cout)
+            for k, br in enumerate(I.branches):
+                h = a
+                if k == 3:
+                    h, I._bidx = cnn.maxpool3(a, 1, out=_nhwc(I.bp, nb, I.hw, I.cin),
+                                              idx=_nhwc(I.bidx, nb, I.hw, I.cin))
+                h = _chain_fwd(E, br, h, nb, train)
+                L = br[-1]
+                L.fwd(h, nb, L.stats if train else None, ws)
+                E._bn(L, L.view(L.z, nb), I.slice(out, k), train, True)    # its channel slice of the concat
+            a = out
+            if I.pool_after:
+                a, I._sidx = cnn.maxpool3(out, 2, out=_nhwc(I.sp, nb, I.out_hw, I.cout),
+                                          idx=_nhwc(I.sidx, nb, I.out_hw, I.cout))
+        return a
 
-def _plan_googlenet(m, rows, dev, dt):
-    return _GoogPlan(m, rows, dev, dt)
+    def backward(self, E, x: torch.Tensor, nb: int, dhead: torch.Tensor) -> None:
+        ws = E.wgrad_ws
+        p = self.pre
+        g = dhead                                          # grad wrt the current module's result
+        for i in range(len(self.mods) - 1, -1, -1):
+            I = self.mods[i]
+            if i > 0:                                      # the module input and where its grad goes
+                J = self.mods[i - 1]
+                a = _nhwc(J.sp if J.pool_after else J.out, nb, J.out_hw, J.cout)
+                dx = _nhwc(J.dsp if J.pool_after else J.dout, nb, J.out_hw, J.cout)
+            else:
+                a, dx = p.view(p.y, nb), p.view(p.dy, nb)
+            if I.pool_after:
+                g = cnn.maxpool3_bwd(g, I._sidx, (nb, I.hw, I.hw, I.cout), 2, out=_nhwc(I.dout, nb, I.hw, I.cout))
+            out = _nhwc(I.out, nb, I.hw, I.cout)
+            for k, br in enumerate(I.branches):
+                E._bn_bwd(br[-1], nb, I.slice(g, k), None, I.slice(out, k))
+                _chain_bwd(E, br, nb, fuse=True)
+                v = br[0]
+                if k < 3:                                  # branch heads: the module input's grad fan-in
+                    E._wgrad(v, a, nb)
+                    v.dgrad(nb, dx, ws, accumulate=k > 0)
+                else:
+                    E._wgrad(v, _nhwc(I.bp, nb, I.hw, I.cin), nb)
+                    dbp = v.dgrad(nb, _nhwc(I.dbp, nb, I.hw, I.cin), ws)
+                    cnn.maxpool3_bwd(dbp, I._bidx, (nb, I.hw, I.hw, I.cin), 1, out=dx, accumulate=True)
+            g = dx
+        E._bn_bwd(p, nb, p.view(p.dy, nb), None, p.view(p.y, nb))
+        E._wgrad(p, x, nb)
 
 
 PLANS = {ResNet: _plan_resnet, MobileNet: _plan_mobilenet, MobileNetV2: _plan_mobilenetv2, VGG: _plan_vgg,
-         PreActResNet: _plan_preact, GoogLeNet: _plan_googlenet}
+         PreActResNet: _PreActPlan, GoogLeNet: _GoogPlan}
 
 
 def supports(model: nn.Module) -> bool:
@@ -453,7 +645,7 @@ class CNNNativeTrainer(LocalTrainer):
         torch.manual_seed(cfg.seed)
         model = build_model(model_name)
         if type(model) not in PLANS:
-            raise TypeError(f"{model_name}: no native plan (ResNet, PreActResNet, MobileNet, MobileNetV2, VGG)")
+            raise TypeError(f"{model_name}: no native plan ({', '.join(t.__name__ for t in PLANS)})")
         if init_state is not None:
             model.load_state_dict(init_state)
         self.model = model.to(device)
@@ -468,22 +660,11 @@ class CNNNativeTrainer(LocalTrainer):
                 s.y = s.y.to(torch.int32)
         self.eval_bs = min(cfg.eval_batch_size, 500)
         self.rows = R = max(cfg.batch_size, self.eval_bs)
-        plan = PLANS[type(model)](self.model, R, device, act_dtype)
-        self.preact = plan if isinstance(plan, _PreActPlan) else None
-        self.goog = plan if isinstance(plan, _GoogPlan) else None
-        if self.goog is not None:
-            self.blocks = []
-            self.head_hw, self.head_c = plan.head_hw, plan.head_c
-            self.units: List[_Unit] = plan.units()
-            self._no_dgrad = {id(plan.pre)}
-        else:
-            self.blocks = plan.blocks if self.preact else plan
-            last = self.blocks[-1]
-            self.head_hw, self.head_c = last.out_hw, last.cout
-            self.units = plan.units() if self.preact else [u for b in self.blocks for u in b.units()]
-            # units whose data gradient is never needed (they read the network input)
-            self._no_dgrad = ({id(self.preact.stem)} if self.preact else
-                              {id(u) for u in self.blocks[0].units()} if self.blocks[0].first else set())
+        self.plan = PLANS[type(model)](self.model, R, device, act_dtype)
+        self.head_hw, self.head_c = self.plan.head_hw, self.plan.head_c
+        self.units: List[_Unit] = self.plan.units()
+        # units whose data gradient is never needed (they read the network input)
+        self._no_dgrad = {id(u) for u in self.plan.no_dgrad}
         # per-step accumulators: BN batch stats [2][O] and BN-backward sums [3][O], one fill each
         # fp64 accumulators: the kernels add fp32 workgroup partials with fp64 atomics (order-independent sums)
         self.stats_all = torch.zeros(sum(conv.STAT_REP * 2 * u.O for u in self.units), dtype=torch.float64,
@@ -543,18 +724,6 @@ class CNNNativeTrainer(LocalTrainer):
             u.bn_rep = self.bn_chain[co:co + n] if n else None
             u.bn_reps = nf // (3 * u.O)
             co += n
-        # BN-backward channel sums taken in the epilogue of the DGRAD that writes the BN's output grad
-        # (conv_igemm.hip BnSums): no separate reduce pass over (dy, z, y)
-        self._fuse_bn_bwd = True
-        # a ReLU'd BN inside a block (no residual): the forward stores its scale / shift, and the backward
-        # derives the ReLU mask from z (z * sc + sh > 0) instead of re-reading the materialised y
-        for u in self.units:
-            u.zco = None
-        if self._fuse_bn_bwd and self.preact is None and self.goog is None:
-            for b in self.blocks:
-                for v in b.main[:-1]:
-                    if v.relu and v.bn_rep is not None:
-                        v.zco = torch.empty(2, v.O, device=device)
         self.xin = torch.empty(R, 32, 32, 8, dtype=act_dtype, device=device)
         self.dhead = torch.empty(R * self.head_hw * self.head_hw * self.head_c, dtype=act_dtype, device=device)
         self.pooled = torch.empty(R, self.head_c, device=device)
@@ -644,55 +813,33 @@ class CNNNativeTrainer(LocalTrainer):
         self._starts, self._sizes = [], []
         self._graphs.clear()
 
-    def _act(self, b: "_Block", nb: int):
-        return b.out_view(nb)
-
-    # ---- kernel schedule ---------------------------------------------------------------------
-    def _bn(self, u: _Unit, z: torch.Tensor, y: torch.Tensor, train: bool, relu: bool, **kw) -> torch.Tensor:
-        return cnn.bn_apply(z, u.bn_args(u.stats), y, train, relu, eps=BN_EPS, momentum=BN_MOM, **kw)
-
+    # ---- kernel schedule: the plan's forward / backward, and the services they launch through ------------
     def _forward(self, nb: int, train: bool, images: torch.Tensor, labels: torch.Tensor, dbase, stats_row: int):
-        if self.preact is not None:
-            return self._forward_preact(nb, train, images, labels, dbase, stats_row)
-        if self.goog is not None:
-            return self._forward_goog(nb, train, images, labels, dbase, stats_row)
         x = cnn.prep_input(images, 0, nb, self.augment and train, self.cfg.seed, self.round_ctr,
                            out=self.xin[:nb], dbase=dbase)
-        a = x
-        for b in self.blocks:
-            h = a
-            ws = self.wgrad_ws
-            for v in b.main[:-1]:
-                v.fwd(h, nb, v.stats if train else None, ws)
-                h = self._bn(v, v.view(v.z, nb), v.view(v.y, nb), train, v.relu,
-                             co_out=v.zco if train else None)
-            last = b.main[-1]
-            last.fwd(h, nb, last.stats if train else None, ws)
-            out = b.pre_view(nb)
-            z = last.view(last.z, nb)
-            if b.shortcut == "proj":
-                p = b.proj
-                p.fwd(a, nb, p.stats if train else None, ws)
-                self._bn(last, z, out, train, b.out_relu, z2=p.view(p.z, nb), b=p.bn_args(p.stats))
-            elif b.shortcut == "identity":
-                self._bn(last, z, out, train, b.out_relu, res=a)
-            else:
-                self._bn(last, z, out, train, b.out_relu)
-            if b.pool:
-                cnn.maxpool2(out, out=b.out_view(nb))
-            a = self._act(b, nb)
+        a = self.plan.forward(self, x, nb, train)
+        return x, self._head(a, nb, train, labels, dbase, stats_row)
+
+    def _backward(self, nb: int, x: torch.Tensor, dhead: torch.Tensor) -> None:
+        self.plan.backward(self, x, nb, dhead)
+
+    def _head(self, a, nb, train, labels, dbase, stats_row):
         lin = self.head_lin
         hd = self.dhead[: a.numel()].view_as(a)
         cnn.head(a, labels, 0, lin.weight, lin.bias, self.stats[stats_row], train, self.pooled[:nb], self.dlog[:nb],
                  hd if train else None, lin.weight.grad if train else None, lin.bias.grad if train else None,
                  dbase=dbase, zero=self.bn_chain if train else None, lossv=self.lossv[:nb])
-        return x, hd
+        return hd
+
+    def _bn(self, u: _Unit, z: torch.Tensor, y: torch.Tensor, train: bool, relu: bool, **kw) -> torch.Tensor:
+        return cnn.bn_apply(z, u.bn_args(u.stats), y, train, relu, eps=BN_EPS, momentum=BN_MOM, **kw)
 
     def _sums(self, conv_u: _Unit, u: _Unit, nb: int, y, zb: Optional[_Unit] = None,
               add: bool = False) -> Optional[dict]:
-        """BN-sums descriptor for ``u``'s BN, taken by ``conv_u``'s DGRAD epilogue (None: not fusable).
-        ``add``: the DGRAD must also add a second incoming grad (a shortcut's)."""
-        if not (self._fuse_bn_bwd and u.bn_rep is not None and u.bn_reps > 0 and conv_u.dgrad_fusable(add)):
+        """BN-sums descriptor for ``u``'s BN, taken by ``conv_u``'s DGRAD epilogue (conv_igemm.hip BnSums: no
+        separate reduce pass over (dy, z, y)); None: not fusable.  ``add``: the DGRAD must also add a second
+        incoming grad (a shortcut's)."""
+        if not (u.bn_rep is not None and u.bn_reps > 0 and conv_u.dgrad_fusable(add)):
             return None
         d = dict(rep=u.bn_rep, reps=u.bn_reps, z=u.view(u.z, nb), y=y, mean=u.smean, inv=u.sinv)
         if zb is not None:
@@ -719,193 +866,6 @@ class CNNNativeTrainer(LocalTrainer):
         cnn.bn_bwd(dya, u.view(u.z, nb), u.bn_args(None), u.bn.weight.grad, u.bn.bias.grad, u.view(u.dz, nb), u.red,
                    dyb=dyb, y=y, gout=gout, ws=bn_ws, dadd=dadd, chained=chained, mask_bn=mask_bn,
                    presummed=presummed, **kw)
-
-    def _backward(self, nb: int, x: torch.Tensor, dhead: torch.Tensor) -> None:
-        if self.preact is not None:
-            return self._backward_preact(nb, x, dhead)
-        if self.goog is not None:
-            return self._backward_goog(nb, x, dhead)
-        dya, dyb, pres = dhead, None, False
-        ws = self.wgrad_ws
-        for i in range(len(self.blocks) - 1, -1, -1):
-            b = self.blocks[i]
-            prev = None if b.first else self.blocks[i - 1]
-            a_in = x if b.first else self._act(prev, nb)
-            last = b.main[-1]
-            din_b = b.in_view(b.din_b, nb) if b.din_b is not None else None
-            if b.pool:   # grad wrt the pooled output -> grad wrt the pre-pool activation
-                dya = cnn.maxpool2_bwd(b.pre_view(nb), dya, out=b.dpre_view(nb))
-            # pres: the next block's first DGRAD wrote dya = (its grad + the shortcut grad) and this BN's sums
-            self._bn_bwd(last, nb, dya, dyb, b.pre_view(nb) if b.out_relu else None, zb=b.proj,
-                         gout=din_b if b.shortcut == "identity" else None, presummed=pres)
-            proj_done = False
-            for j in range(len(b.main) - 1, -1, -1):
-                v = b.main[j]
-                xin = b.main[j - 1].view(b.main[j - 1].y, nb) if j > 0 else a_in
-                self._wgrad(v, xin, nb)
-                if j > 0:
-                    w = b.main[j - 1]
-                    wy = w.view(w.y, nb) if w.relu else None
-                    bs = self._sums(v, w, nb, wy)
-                    msc = None
-                    if bs is not None and w.zco is not None:   # ReLU mask from z: y is not re-read
-                        bs.update(y=None, msc=w.zco)
-                        wy, msc = None, w.zco
-                    v.dgrad(nb, w.view(w.dy, nb), ws, bn_sums=bs)
-                    self._bn_bwd(w, nb, w.view(w.dy, nb), None, wy, presummed=bs is not None, mask_bn=msc)
-                elif not b.first:
-                    din_a = b.in_view(b.din_a, nb)
-                    bs = None
-                    if not prev.pool:
-                        pl = prev.main[-1]
-                        bs = self._sums(v, pl, nb, prev.pre_view(nb) if prev.out_relu else None, zb=prev.proj,
-                                        add=din_b is not None)
-                    if bs is not None:
-                        # the shortcut's grad first, then conv1's DGRAD adds it and takes the previous
-                        # block's BN-backward sums from the complete grad
-                        if b.proj is not None:
-                            self._wgrad(b.proj, a_in, nb)
-                            b.proj.dgrad(nb, din_b, ws)
-                            proj_done = True
-                        v.dgrad(nb, din_a, ws, add=din_b, bn_sums=bs)   # add=None: no shortcut
-                        dya, dyb, pres = din_a, None, True
-                    else:
-                        v.dgrad(nb, din_a, ws)
-                        dya, dyb, pres = din_a, din_b, False
-            if b.proj is not None and not proj_done:
-                self._wgrad(b.proj, a_in, nb)
-                b.proj.dgrad(nb, din_b, ws)
-
-    # ---- pre-activation ResNets --------------------------------------------------------------
-    def _head(self, a, nb, train, labels, dbase, stats_row):
-        lin = self.head_lin
-        hd = self.dhead[: a.numel()].view_as(a)
-        cnn.head(a, labels, 0, lin.weight, lin.bias, self.stats[stats_row], train, self.pooled[:nb], self.dlog[:nb],
-                 hd if train else None, lin.weight.grad if train else None, lin.bias.grad if train else None,
-                 dbase=dbase, zero=self.bn_chain if train else None, lossv=self.lossv[:nb])
-        return hd
-
-    def _forward_preact(self, nb: int, train: bool, images, labels, dbase, stats_row: int):
-        P, ws = self.preact, self.wgrad_ws
-        x = cnn.prep_input(images, 0, nb, self.augment and train, self.cfg.seed, self.round_ctr,
-                           out=self.xin[:nb], dbase=dbase)
-        st = P.stem
-        st.fwd(x, nb, st.stats if train else None, ws)
-        self._bn(st, st.view(st.z, nb), st.view(st.y, nb), train, True)
-        prev = st
-        for b in P.blocks:
-            a = prev.view(prev.y, nb)                      # relu(bn1(x_b))
-            h = a
-            for u in b.units[:-1]:
-                u.fwd(h, nb, u.stats if train else None, ws)
-                self._bn(u, u.view(u.z, nb), u.view(u.y, nb), train, True)
-                h = u.view(u.y, nb)
-            if b.sc is not None:
-                b.sc.fwd(a, nb, None, ws)
-                skip = b.sc.view(b.sc.z, nb)
-            else:
-                skip = prev.view(prev.z, nb)               # identity: x_b
-            L = b.units[-1]
-            L.fwd(h, nb, L.stats if (train and L.bn is not None) else None, ws, res=skip)
-            if L.bn is not None:
-                self._bn(L, L.view(L.z, nb), L.view(L.y, nb), train, True)
-            prev = L
-        return x, self._head(prev.view(prev.z, nb), nb, train, labels, dbase, stats_row)
-
-    def _backward_preact(self, nb: int, x: torch.Tensor, dhead: torch.Tensor) -> None:
-        P, ws = self.preact, self.wgrad_ws
-        g = dhead                                          # dL / d x_{b+1} (= dz of the block's last unit)
-        for bi in range(len(P.blocks) - 1, -1, -1):
-            b = P.blocks[bi]
-            prev = P.blocks[bi - 1].units[-1] if bi > 0 else P.stem
-            a = prev.view(prev.y, nb)
-            L = b.units[-1]
-            pen = b.units[-2]
-            self._wgrad(L, pen.view(pen.y, nb), nb, dz=g)
-            L.dgrad(nb, pen.view(pen.dy, nb), ws, dz=g)
-            for j in range(len(b.units) - 2, -1, -1):
-                u = b.units[j]
-                self._bn_bwd(u, nb, u.view(u.dy, nb), None, u.view(u.y, nb))
-                if j > 0:
-                    w = b.units[j - 1]
-                    self._wgrad(u, w.view(w.y, nb), nb)
-                    u.dgrad(nb, w.view(w.dy, nb), ws)
-                else:
-                    self._wgrad(u, a, nb)
-                    u.dgrad(nb, prev.view(prev.dy, nb), ws)      # d a_b, conv1 branch
-            da2 = None
-            if b.sc is not None:                           # d a_b, shortcut-conv branch
-                self._wgrad(b.sc, a, nb, dz=g)
-                da2 = b.in_view(b.da2, nb)
-                b.sc.dgrad(nb, da2, ws, dz=g)
-            # bn1 of this block (prev's BN): dx_b = BN_bwd(relu mask) + identity-shortcut grad
-            self._bn_bwd(prev, nb, prev.view(prev.dy, nb), da2, a, dadd=None if b.sc is not None else g)
-            g = prev.view(prev.dz, nb)
-        self._wgrad(P.stem, x, nb)
-
-    # ---- GoogLeNet ----------------------------------------------------------------------------
-    def _forward_goog(self, nb: int, train: bool, images, labels, dbase, stats_row: int):
-        G, ws = self.goog, self.wgrad_ws
-        x = cnn.prep_input(images, 0, nb, self.augment and train, self.cfg.seed, self.round_ctr,
-                           out=self.xin[:nb], dbase=dbase)
-        p = G.pre
-        p.fwd(x, nb, p.stats if train else None, ws)
-        a = self._bn(p, p.view(p.z, nb), p.view(p.y, nb), train, True)
-        for I in G.mods:
-            out = I.out_view(I.out, nb)
-            for k, br in enumerate(I.branches):
-                h = a
-                if k == 3:
-                    h, I._bidx = cnn.maxpool3(a, 1, out=I.in_view(I.bp, nb), idx=I.in_view(I.bidx, nb))
-                for u in br[:-1]:
-                    u.fwd(h, nb, u.stats if train else None, ws)
-                    h = self._bn(u, u.view(u.z, nb), u.view(u.y, nb), train, True)
-                L = br[-1]
-                L.fwd(h, nb, L.stats if train else None, ws)
-                self._bn(L, L.view(L.z, nb), I.slice(out, k), train, True)    # its channel slice of the concat
-            a = out
-            if I.pool_after:
-                a, I._sidx = cnn.maxpool3(out, 2, out=I.final_view(I.sp, nb), idx=I.final_view(I.sidx, nb))
-        return x, self._head(a, nb, train, labels, dbase, stats_row)
-
-    def _backward_goog(self, nb: int, x: torch.Tensor, dhead: torch.Tensor) -> None:
-        G, ws = self.goog, self.wgrad_ws
-        p = G.pre
-        g = dhead                                          # grad wrt the current module's result
-        for i in range(len(G.mods) - 1, -1, -1):
-            I = G.mods[i]
-            if i > 0:                                      # the module input and where its grad goes
-                J = G.mods[i - 1]
-                a = J.final_view(J.sp if J.pool_after else J.out, nb)
-                dx = J.final_view(J.dsp if J.pool_after else J.dout, nb)
-            else:
-                a, dx = p.view(p.y, nb), p.view(p.dy, nb)
-            if I.pool_after:
-                g = cnn.maxpool3_bwd(g, I._sidx, (nb, I.hw, I.hw, I.cout), 2, out=I.out_view(I.dout, nb))
-            out = I.out_view(I.out, nb)
-            for k, br in enumerate(I.branches):
-                self._bn_bwd(br[-1], nb, I.slice(g, k), None, I.slice(out, k))
-                for j in range(len(br) - 1, -1, -1):
-                    v = br[j]
-                    if j > 0:
-                        w = br[j - 1]
-                        wy = w.view(w.y, nb)
-                        self._wgrad(v, wy, nb)
-                        # the inner BN's backward sums in this DGRAD's epilogue where it runs on conv_tap
-                        # (no separate reduce pass over (dy, z, y))
-                        bs = self._sums(v, w, nb, wy)
-                        v.dgrad(nb, w.view(w.dy, nb), ws, bn_sums=bs)
-                        self._bn_bwd(w, nb, w.view(w.dy, nb), None, wy, presummed=bs is not None)
-                    elif k < 3:                            # branch heads: the module input's grad fan-in
-                        self._wgrad(v, a, nb)
-                        v.dgrad(nb, dx, ws, accumulate=k > 0)
-                    else:
-                        self._wgrad(v, I.in_view(I.bp, nb), nb)
-                        dbp = v.dgrad(nb, I.in_view(I.dbp, nb), ws)
-                        cnn.maxpool3_bwd(dbp, I._bidx, (nb, I.hw, I.hw, I.cin), 1, out=dx, accumulate=True)
-            g = dx
-        self._bn_bwd(p, nb, p.view(p.dy, nb), None, p.view(p.y, nb))
-        self._wgrad(p, x, nb)
 
     def _sgd(self) -> None:
         c, fs = self.cfg, self.fs
@@ -1023,7 +983,3 @@ class CNNNativeTrainer(LocalTrainer):
 
     def eval_stats(self) -> EpochStats:
         return self._read_stats(1)
-
-
-# backwards-compatible name
-ResNetNativeTrainer = CNNNativeTrainer
