@@ -11,87 +11,12 @@
 #include <string>
 #include <vector>
 
+#include "kernels/cnn_ops.h"
 #include "kernels/common.h"
+#include "kernels/conv.h"
 #include "kernels/wgrad_reduce.h"
 
 namespace py = pybind11;
-
-namespace fedmi {
-struct ConvShape {
-  int N, H, W, C, Cw, O, P, Q, R, S, st, pad;
-};
-void launch_conv_fwd(hipStream_t, const ConvShape&, const bf16*, const bf16*, bf16*, double*, const float*, float*, long,
-                     const bf16*);
-void launch_conv_dgrad(hipStream_t, const ConvShape&, const bf16*, const bf16*, bf16*, float*, long, const bf16*, int,
-                       const bf16*, const BnSums*);
-int conv_dgrad_fusable(const ConvShape&, int);
-struct DPackItem {
-  const float* w;
-  bf16* wd;
-  int O, Cw, C, R, S, st, pad;
-};
-void launch_dgrad_pack_multi(hipStream_t, const DPackItem*, int);
-long conv_fd_ws_floats(const ConvShape&);
-struct PackItem {
-  const float* w;
-  bf16* wr;
-  int O, Cw, C, RS;
-  int O8;
-  int G;
-};
-void launch_conv_pack_multi(hipStream_t, const PackItem*, int);
-void launch_conv_wgrad(hipStream_t, const ConvShape&, const bf16*, const bf16*, float*, float*, long, int, int, int, int,
-                       WredItem*, int);
-long conv_wgrad_ws_floats(const ConvShape&);
-void launch_conv_pack(hipStream_t, const float*, bf16*, int, int, int, int, int, int);
-struct SgdPackConv {
-  long off;
-  bf16* wr;
-  bf16* wd;
-  int O, Cw, C, R, S, st, pad;
-};
-struct SgdPackPlan {
-  std::vector<char> table;
-  int n_entries, n_blocks, lds_bytes;
-};
-SgdPackPlan build_sgd_pack_plan(const SgdPackConv*, int, const long*, int);
-void launch_sgd_pack(hipStream_t, const void*, int, int, int, float*, const float*, float*, float, float, float, float,
-                     int, int);
-
-struct BNDesc {
-  const double* stats; const float* gamma; const float* beta; float* rmean; float* rvar; long long* nbt;
-  float* smean; float* sinv; const float* shift; const float* cbias;
-};
-void launch_maxpool2(hipStream_t, const bf16*, bf16*, int, int, int, int);
-void launch_maxpool3(hipStream_t, const bf16*, bf16*, uint8_t*, int, int, int, int, int);
-void launch_maxpool3_bwd(hipStream_t, const bf16*, const uint8_t*, bf16*, int, int, int, int, int, int);
-void launch_maxpool2_bwd(hipStream_t, const bf16*, const bf16*, bf16*, int, int, int, int);
-struct BNBwdDesc {
-  const bf16* dya; const bf16* dyb; const bf16* y;
-  const bf16* za; const float* meanA; const float* invA; const float* gammaA; float* dgammaA; float* dbetaA; bf16* dza;
-  const bf16* zb; const float* meanB; const float* invB; const float* gammaB; float* dgammaB; float* dbetaB; bf16* dzb;
-  bf16* gout;
-  float* shiftA; float* shiftB;
-  const bf16* dadd;
-  const float* msc;
-};
-struct DwShape {
-  int N, H, W, C, R, S, st, pad;
-};
-void launch_dw_fwd(hipStream_t, const DwShape&, const bf16*, const float*, bf16*, double*, const float*);
-void launch_dw_dgrad(hipStream_t, const DwShape&, const bf16*, const float*, bf16*, const BnSums*);
-long dw_wgrad_ws_floats(const DwShape&);
-void launch_dw_wgrad(hipStream_t, const DwShape&, const bf16*, const bf16*, float*, float*, long, int, WredItem*);
-void launch_prep_input(hipStream_t, const uint8_t*, int, const int*, int, int, uint32_t, const int*, bf16*);
-void launch_sched_next(hipStream_t, const int*, int*, int*, double*, long);
-void launch_bn_apply(hipStream_t, const bf16*, const BNDesc&, const bf16*, const BNDesc*, const bf16*, bf16*, int, int,
-                     float, float, int, int, int, float*);
-void launch_bn_bwd(hipStream_t, const BNBwdDesc&, double*, int, int, double*, long, int, int, int, int);
-long bn_bwd_ws_floats(int, int);
-int bn_bwd_chain_reps(int);
-void launch_head(hipStream_t, const bf16*, const int*, int, const int*, int, int, int, int, const float*,
-                 const float*, float*, float*, bf16*, float*, float*, float*, float*, int, float*, long);
-}  // namespace fedmi
 
 using namespace fedmi;
 

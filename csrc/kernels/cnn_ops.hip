@@ -23,6 +23,7 @@
 // (src/models/resnet.py:14-104, src/main.py:146-156).
 #include <stdexcept>
 
+#include "cnn_ops.h"
 #include "common.h"
 
 namespace {
@@ -928,11 +929,6 @@ dim3 apply_grid(int M, int C) {
 
 namespace fedmi {
 
-struct BNDesc {
-  const double* stats; const float* gamma; const float* beta; float* rmean; float* rvar; long long* nbt;
-  float* smean; float* sinv; const float* shift; const float* cbias;
-};
-
 static BNArgs to_args(const BNDesc& d) {
   return BNArgs{d.stats, d.gamma, d.beta, d.rmean, d.rvar, d.nbt, d.smean, d.sinv, d.shift, d.cbias};
 }
@@ -1134,16 +1130,6 @@ void launch_bn_apply(hipStream_t st, const bf16* z, const BNDesc& a, const bf16*
   }
 }
 
-
-struct BNBwdDesc {
-  const bf16* dya; const bf16* dyb; const bf16* y;
-  const bf16* za; const float* meanA; const float* invA; const float* gammaA; float* dgammaA; float* dbetaA; bf16* dza;
-  const bf16* zb; const float* meanB; const float* invB; const float* gammaB; float* dgammaB; float* dbetaB; bf16* dzb;
-  bf16* gout;
-  float* shiftA; float* shiftB;
-  const bf16* dadd;
-  const float* msc;
-};
 
 static void bn_bwd_grid(int M, int C, int* tb, int* rows_per_block, int* nblk) {
   const int VR = C / 8;

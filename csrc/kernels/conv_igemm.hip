@@ -24,20 +24,30 @@
 //
 // Epilogues: FWD writes bf16 Y and (optionally) per-channel sum / sum-of-
 // squares for the following BatchNorm (training batch statistics fused into
-// the conv); DGRAD writes bf16 dX; WGRAD atomically adds the
-// fp32 partial into the PyTorch-layout [O][C][R][S] gradient (split-K over
-// output pixels, gridDim.z splits).
+// the conv); DGRAD writes bf16 dX; WGRAD stores the fp32
+// partial of each K split (split-K over output pixels, gridDim.z splits) as
+// its own [O][R][S][C] plane of a workspace, and one reduce launch sums the
+// planes in fixed order into the PyTorch-layout [O][C][R][S] gradient: no
+// atomics, bit-stable.  FWD / DGRAD split-K works the same way through
+// conv_splitk_reduce.
+//
+// Layout of this file: the kernels, then thin launchers.  Every routing
+// decision (kernel, tile, K split, workspace) is made in conv_plan.h; the POD
+// geometry the kernels take by value is in conv_geom.h, the public interface
+// in conv.h.
 //
 // Reference parity: these are the convolution / convolution_backward ops of
 // every zoo model (src/models/resnet.py:14-104 etc.).
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <vector>
 #include <stdexcept>
 
 #include "common.h"
+#include "conv.h"
+#include "conv_geom.h"
+#include "conv_plan.h"
 #include "wgrad_reduce.h"
 
 // diagnostic build (-DFEDMI_STAMPS): s_memtime per conv_tap phase, lane 0 of each workgroup
@@ -68,32 +78,8 @@ void read_conv_stamps(unsigned long long* host, bool clear) {
 
 namespace {
 
-struct FastDiv {   // q = x / d for 0 <= x < 2^31 (Granlund-Montgomery)
-  uint32_t d, m, s;
-};
 FEDMI_DEV uint32_t fdiv(uint32_t x, const FastDiv& f) { return (__umulhi(x, f.m) + x) >> f.s; }
 
-struct ConvGeom {
-  int N, H, W, C;          // input (C = padded channel count, % 8 == 0)
-  int O, P, Q;             // output channels / spatial
-  int R, S, st, pad;
-  int M, NC, K;            // GEMM rows / cols / reduction for the launched mode
-  int Cw;                  // channel count of the fp32 master weight (unpadded; WGRAD epilogue)
-  // DGRAD sub-pixel phase (stride 2: one launch per output parity (ph, pw), each
-  // summing only the taps r = r0 + 2i, s = s0 + 2j that land on that parity;
-  // stride 1: ph = pw = 0, r0 = s0 = 0, nr = R, ns = S, Hp = H, Wp = W)
-  int ph, pw, r0, s0, nr, ns, Hp, Wp;
-  FastDiv dC, dO, dS, dQ, dPQ, dW, dHW, dNS, dWp, dHWp;
-};
-
-// GEMM row m = (n, p, q) over an output grid P x Q -> row of the stored output:
-// identity, or the stride-`st` sub-pixel scatter of a DGRAD phase:
-// ((n * OH + p * st + ph) * OW + q * st + pw).
-struct RowMap {
-  int on;
-  int P, Q, OH, OW, st, ph, pw;
-  FastDiv dPQ, dQ;
-};
 FEDMI_DEV long map_row(const RowMap& r, int m) {
   if (!r.on) return m;
   const uint32_t n = fdiv(m, r.dPQ), pq = m - n * r.P * r.Q;
@@ -104,7 +90,6 @@ FEDMI_DEV long map_row(const RowMap& r, int m) {
 using fedmi::BnSums;
 
 enum { FWD = 0, DGRAD = 1, WGRAD = 2 };
-constexpr int BK = 64;
 constexpr int KC_LD = BK + 8;   // KC image row stride (elements): 144 B = 9 x 16 B
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -456,17 +441,8 @@ __global__ __launch_bounds__(256) void conv_igemm(const bf16* __restrict__ x, co
 //
 // Pipeline: three LDS stages, the DMA two K steps ahead, ONE raw s_barrier per
 // step behind a counted `s_waitcnt vmcnt` (never vmcnt(0) or __syncthreads()
-// while a DMA is in flight).  Tile 128 x BN (BN 128 | 64), 4 waves of 64 x BN/2.
+// while a DMA is in flight).  Tile 128 x BN (BN 128 | 64), NW waves of 128 / (NW / 2) x BN/2.
 // ---------------------------------------------------------------------------
-struct TapGeom {
-  int N, H, W, C;          // input [N][H][W][C], C % 64 == 0
-  int O;                   // GEMM columns = weight rows [O][R][S][C]
-  int P, Q;                // output grid, GEMM rows M = N * P * Q
-  int R, S, st, pad_h, pad_w;
-  int M, K;                // K = R * S * C
-  FastDiv dPQ, dQ;
-};
-
 __device__ __attribute__((aligned(16))) const uint4 g_zero16[4] = {};
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -504,8 +480,9 @@ FEDMI_DEV bf16x8 frag_sw(const bf16* img, int i0, int kk, int lane) {
 // Three LDS stages, the DMA two K steps ahead (1 workgroup per CU at BN 128, 2 at BN 64).  Measured
 // slower: a two-stage double buffer (one more workgroup per CU), and four stages at BN 128 (128 KiB, the
 // DMA three steps ahead: +5..13 % per conv, profiles/r4_cnn/tap_stages_ab.txt).
-// NW waves per workgroup (4 or 8) in an (NW / 2) x 2 grid over the 128 x BN tile: with 8 waves every SIMD
-// holds two waves, so one wave's barrier / LDS / DMA latency is covered by its partner's MFMAs.
+// NW waves per workgroup in an (NW / 2) x 2 grid over the 128 x BN tile.  Only NW = 8 is instantiated: every SIMD
+// holds two waves, so one wave's barrier / LDS / DMA latency is covered by its partner's MFMAs (8-15 % faster per
+// conv than one wave per SIMD, profiles/r5_cnn/).
 // GEN: input channels C % 8 == 0 but not % 64 (GoogLeNet's 16 / 24 / 32 / 48 / 96 / 112 / 144 / 160-channel inception
 // branches, DenseNet's growth): a 64-deep K step then spans several taps, so every DMA lane tracks the (tap, channel)
 // of its own 16-byte chunk (k = 64 t + 8 kc, incrementally, no division in the loop) and the last step's chunks
@@ -869,18 +846,6 @@ __global__ __launch_bounds__(64 * NW) void conv_tap(const bf16* __restrict__ in,
 // The sub-pixel phases of a stride-2 DGRAD in ONE launch: blockIdx.x walks the phases' tiles in order,
 // blockIdx.z is the K split (phases with fewer splits return early, before any barrier).  Each phase
 // writes its own parity rows of dX (row maps), or its split-K partials into its own workspace slice.
-constexpr int MAX_TAP_PHASES = 4;
-struct TapMulti {
-  TapGeom g[MAX_TAP_PHASES];
-  RowMap rm[MAX_TAP_PHASES];
-  long woff[MAX_TAP_PHASES];       // weight-image offset (elements)
-  long wsoff[MAX_TAP_PHASES];      // workspace offset (floats), -1: no split (the epilogue writes dX)
-  int kps[MAX_TAP_PHASES];         // K steps per split
-  int splits[MAX_TAP_PHASES];
-  int tile0[MAX_TAP_PHASES + 1];   // first tile of each phase; tile0[n] = total
-  int n;
-};
-
 template <int BN, int NW>
 __global__ __launch_bounds__(64 * NW) void conv_tap_phases(const bf16* __restrict__ in, const bf16* __restrict__ wt,
                                                        bf16* __restrict__ out, float* __restrict__ ws,
@@ -893,20 +858,6 @@ __global__ __launch_bounds__(64 * NW) void conv_tap_phases(const bf16* __restric
                     tm.rm[p], tm.kps[p], split ? nullptr : res, split ? BnSums{} : bs,
                     (int)blockIdx.x - tm.tile0[p], blockIdx.z);
 }
-
-// ---------------------------------------------------------------------------
-// Halo-patch geometry for 3x3 / stride 1 / pad 1: a 128-pixel tile is IMGS images x TH rows x W
-// columns whose input window (TH + 2 rows x W + 2 columns per image, zero halo) is DMA'd into LDS
-// once per 64-channel chunk; the nine taps read shifted rows of the same patch (conv_wgrad_halo).
-// ---------------------------------------------------------------------------
-struct HaloGeom {
-  int N, H, W, C, O;
-  int M, K;                // M = N * H * W output pixels, K = 9 * C (weight row length)
-  int TH, IMGS;            // tile = IMGS images x TH rows x W columns = 128 pixels
-  int PW, NPR;             // patch row width W + 2, patch rows IMGS * (TH + 2) * (W + 2)
-  int nchunks;             // C / 64
-  FastDiv dPI, dPW, dTHW, dW, dHW;   // by (TH + 2) * PW, PW, TH * W, W, H * W
-};
 
 // s_waitcnt vmcnt(n) for a run-time n <= N (expcnt / lgkmcnt left at their maxima)
 template <int N>
@@ -936,12 +887,12 @@ FEDMI_DEV void vm_wait_le(int n) {
 // ---------------------------------------------------------------------------
 // KR = 1: the same kernel for a 1x1 / stride-1 conv -- the "patch" is the block's own 128 pixel rows (no halo,
 // one tap), dW[o][c] = sum_m dY[m][o] X[m][c]: a plain GEMM over the pixels with both operands pixel-major.
-template <int PP, int KR = 3>
+template <int KR = 3>
 __global__ __launch_bounds__(256) void conv_wgrad_halo(const bf16* __restrict__ x, const bf16* __restrict__ dy,
                                                        float* __restrict__ ws, HaloGeom g, int blocks_per_split) {
   constexpr int TAPS = KR * KR;
-  constexpr int PCAP = KR == 1 ? 128 : PP == 1 ? 208 : 288;
-  constexpr int NPS = KR == 1 ? 4 : 7 * PP;   // patch wave-instructions per block per wave
+  constexpr int PCAP = KR == 1 ? 128 : 208;   // patch rows (wgrad_halo_geom: NPR <= 208)
+  constexpr int NPS = KR == 1 ? 4 : 7;        // patch wave-instructions per block per wave
   constexpr int DYE = 128 * 64;           // dY stage elements
   constexpr int PTE = PCAP * 64;          // patch stage elements
   constexpr int NST = 3;
@@ -1206,10 +1157,6 @@ __global__ __launch_bounds__(256) void dgrad_pack_kernel(DPackTable t) {
 // bf16(y) - shift as in the other epilogues: per-lane sums, 16-lane shuffles, a workgroup LDS combine, fp64
 // replica atomics.
 // ---------------------------------------------------------------------------
-struct StemGeom {
-  int N, H, W, O, M;   // input [N][H][W][8], output [N][H][W][O], M = N * H * W
-};
-
 template <int OT>
 __global__ __launch_bounds__(256) void conv_stem_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wr,
                                                         bf16* __restrict__ y, double* __restrict__ stats,
@@ -1325,7 +1272,6 @@ struct SgdPackEntry {
   int r0[4], s0[4], nr[4], ns[4];
 };
 
-template <int RU>
 __global__ __launch_bounds__(256) void sgd_pack_kernel(const SgdPackEntry* __restrict__ tab, int n,
                                                        float* __restrict__ P, const float* __restrict__ G,
                                                        float* __restrict__ B, float lr, float mom, float wdecay,
@@ -1375,6 +1321,7 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const SgdPackEntry* __res
   // at a wave-uniform base; updated values -> LDS, channels past Cw as zeros.  8 rows x 3 row chunks x 3 operands
   // in flight per lane (RU = 4 rows per pass: 2 measured the same, 8 18-28 % slower -- its VGPRs cost occupancy;
   // profiles/r5_cnn/sgdpack/).
+  constexpr int RU = 4;
   for (int k0 = 0; k0 < 16; k0 += RU) {
     for (int f0 = lane; f0 < span; f0 += 64 * 3) {
       float pv[RU][3], gv[RU][3], bv[RU][3];
@@ -1661,51 +1608,9 @@ __global__ __launch_bounds__(256) void conv_pack_multi_kernel(PackTable t) {
   }
 }
 
-FastDiv make_div(uint32_t d) {
-  FastDiv f;
-  f.d = d;
-  uint32_t s = 0;
-  while ((1ull << s) < d) ++s;
-  f.s = s;
-  f.m = (uint32_t)((((1ull << 32) * ((1ull << s) - d)) / d) + 1);
-  return f;
-}
-
 }  // namespace
 
 namespace fedmi {
-
-struct ConvShape {
-  int N, H, W, C, Cw, O, P, Q, R, S, st, pad;
-};
-
-static RowMap make_rowmap(int P, int Q, int OH, int OW, int st, int ph, int pw) {
-  RowMap r{};
-  r.on = 1;
-  r.P = P; r.Q = Q; r.OH = OH; r.OW = OW; r.st = st; r.ph = ph; r.pw = pw;
-  r.dPQ = make_div(P * Q); r.dQ = make_div(Q);
-  return r;
-}
-
-static ConvGeom make_geom(const ConvShape& s) {
-  ConvGeom g{};
-  g.N = s.N; g.H = s.H; g.W = s.W; g.C = s.C; g.O = s.O; g.P = s.P; g.Q = s.Q;
-  g.R = s.R; g.S = s.S; g.st = s.st; g.pad = s.pad; g.Cw = s.Cw;
-  g.dC = make_div(s.C); g.dO = make_div(s.O); g.dS = make_div(s.S); g.dQ = make_div(s.Q);
-  g.dPQ = make_div(s.P * s.Q); g.dW = make_div(s.W); g.dHW = make_div(s.H * s.W);
-  g.ph = g.pw = 0; g.r0 = g.s0 = 0; g.nr = s.R; g.ns = s.S; g.Hp = s.H; g.Wp = s.W;
-  g.dNS = make_div(s.S); g.dWp = make_div(s.W); g.dHWp = make_div(s.H * s.W);
-  return g;
-}
-
-static void check_shape(const ConvShape& s) {
-  if (s.C % 8 || s.O % 8 || s.C < s.Cw || s.st < 1 || s.st > 2 || s.R < 1 || s.S < 1)
-    throw std::invalid_argument("conv_igemm: need C % 8 == 0, O % 8 == 0, stride 1|2");
-  if (s.P != (s.H + 2 * s.pad - s.R) / s.st + 1 || s.Q != (s.W + 2 * s.pad - s.S) / s.st + 1)
-    throw std::invalid_argument("conv_igemm: inconsistent output size");
-  if ((long)s.N * s.H * s.W * s.C >= (1l << 31) || (long)s.N * s.P * s.Q * s.O >= (1l << 31))
-    throw std::invalid_argument("conv_igemm: tensor too large for 32-bit index math");
-}
 
 static int num_cus() {
   static int n = 0;
@@ -1718,26 +1623,7 @@ static int num_cus() {
   return n;
 }
 
-struct TileCfg {
-  int BM, BN;
-};
-
-static TileCfg pick_tiles(int M, int NC) {
-  const int cus = num_cus();
-  const int BN = NC <= 64 ? 64 : 128;
-  const long t128 = (long)((M + 127) / 128) * ((NC + BN - 1) / BN);
-  return TileCfg{(M > 64 && t128 >= cus) ? 128 : 64, BN};
-}
-
-// WGRAD always splits K, so the tile count never has to fill the chip: take the 128 x 128 tile
-// (twice the MFMA work per loaded byte) for O >= 256 -- measured 44 -> 38 us (256x256 3x3) and
-// 51 -> 47 us (512x512) at batch 128, but slower at O = 128.
-static TileCfg pick_tiles_wgrad(int M, int NC) {
-  TileCfg t = pick_tiles(M, NC);
-  if (M >= 256 && NC > 64) t.BM = 128;
-  return t;
-}
-
+// ---- issuing a plan's launches (conv_plan.h decides, these only launch) ------------------------------------------
 template <int MODE, int BM, int BN>
 static void launch_tiled(hipStream_t st, dim3 grid, const ConvGeom& g, const bf16* x, const bf16* w, const bf16* dy,
                          bf16* out, float* gout, double* stats, const float* shift, int kps, int partial) {
@@ -1745,649 +1631,146 @@ static void launch_tiled(hipStream_t st, dim3 grid, const ConvGeom& g, const bf1
                      partial);
 }
 
-// FWD / DGRAD split-K: GEMMs with fewer output tiles than CUs and a long K loop
-// (ResNet layer3/4 at batch 128: 128-256 tiles, 36-72 K steps) leave most of
-// the chip idle behind a serial K chain.  Split K so that ~3 workgroups per CU
-// run >= 8 K steps each, partials into ``ws``; 1 = no split.
-// The split-K combine (conv_splitk_reduce) gives each lane one 8-channel vector of a row and needs a
-// whole row in one 256-lane block: rows wider than 2048 channels never split.
-static constexpr int SPLITK_MAX_NC = 2048;
-
-static int fd_splits(const ConvGeom& g, long ws_floats) {
-  if (ws_floats <= 0 || g.NC > SPLITK_MAX_NC) return 1;
-  const TileCfg t = pick_tiles(g.M, g.NC);
-  const long tiles = (long)((g.M + t.BM - 1) / t.BM) * ((g.NC + t.BN - 1) / t.BN);
-  const int ksteps = (g.K + BK - 1) / BK;
-  if (tiles >= 2l * num_cus() || ksteps < 16) return 1;
-  long sp = std::min<long>((3l * num_cus() + tiles - 1) / tiles, ksteps / 8);
-  sp = std::min<long>(sp, ws_floats / ((long)g.M * g.NC));
-  if (sp < 2) return 1;
-  const int kps = (int)((ksteps + sp - 1) / sp);
-  return (ksteps + kps - 1) / kps;
-}
-
 template <int MODE>
-static void launch_mode(hipStream_t st, const ConvGeom& g, const bf16* x, const bf16* w, const bf16* dy, bf16* out,
-                        float* gout, double* stats, int splits, const float* shift = nullptr, int partial = 0) {
-  const TileCfg t = MODE == WGRAD ? pick_tiles_wgrad(g.M, g.NC) : pick_tiles(g.M, g.NC);
-  const long tiles = (long)((g.M + t.BM - 1) / t.BM) * ((g.NC + t.BN - 1) / t.BN);
-  const int ksteps = (g.K + BK - 1) / BK;
-  if (MODE != WGRAD && !(partial & 1)) splits = 1;
-  splits = std::max(1, std::min(splits, ksteps));
-  const int kps = std::max(1, (ksteps + splits - 1) / splits);
-  splits = std::max(1, (ksteps + kps - 1) / kps);
-  dim3 grid((unsigned)tiles, 1, (unsigned)splits);
+static void issue_igemm(hipStream_t st, const ConvGeom& g, TileCfg t, unsigned tiles, int kps, int splits, const bf16* x,
+                        const bf16* w, const bf16* dy, bf16* out, float* gout, double* stats, const float* shift,
+                        int partial) {
+  dim3 grid(tiles, 1, (unsigned)splits);
   if (t.BM == 128 && t.BN == 128) launch_tiled<MODE, 128, 128>(st, grid, g, x, w, dy, out, gout, stats, shift, kps, partial);
   else if (t.BM == 128) launch_tiled<MODE, 128, 64>(st, grid, g, x, w, dy, out, gout, stats, shift, kps, partial);
   else if (t.BN == 128) launch_tiled<MODE, 64, 128>(st, grid, g, x, w, dy, out, gout, stats, shift, kps, partial);
   else launch_tiled<MODE, 64, 64>(st, grid, g, x, w, dy, out, gout, stats, shift, kps, partial);
 }
 
-// ---- tap-major LDS-DMA path (conv_tap)
-static TapGeom make_tap(int N, int H, int W, int C, int O, int P, int Q, int R, int S, int st, int pad_h, int pad_w) {
-  TapGeom g{};
-  g.N = N; g.H = H; g.W = W; g.C = C; g.O = O; g.P = P; g.Q = Q;
-  g.R = R; g.S = S; g.st = st; g.pad_h = pad_h; g.pad_w = pad_w;
-  g.M = N * P * Q; g.K = R * S * C;
-  g.dPQ = make_div(P * Q); g.dQ = make_div(Q);
-  return g;
+// the split-K combine of the tap and the generic path alike
+static void issue_combine(hipStream_t st, int M, int NC, const RowMap& rm, const float* ws, int splits, bf16* out,
+                          double* stats, const float* shift, const bf16* res, const BnSums& bs) {
+  const Combine c = combine_geom(M, NC, stats || bs.rep);
+  hipLaunchKernelGGL(conv_splitk_reduce, dim3(c.nblk), dim3(c.tb), 0, st, ws, splits, M, NC, rm, out, stats, shift,
+                     c.rows_per_block, res, bs);
 }
 
-// conv_tap tile width: 128 columns (96 KiB of LDS stages, 1 workgroup per CU) while the 128-wide tiles fill the
-// chip; 64 (72 KiB, 2 per CU) for O <= 64 and for problems whose 128-wide tiles would leave CUs idle (ResNet-18 l3 /
-// l4: 128 / 64 tiles -> 256 / 128; -19 % / -8 % per conv, while l2's 256 tiles stay faster at 128: +7 % at 64,
-// profiles/r5_cnn/).  FEDMI_TAP_BN=64|128 forces one width (A/B runs).  m_tiles: 128-row tiles of the problem.
-static int tap_bn_for(int O, long m_tiles) {
-  static const int force = [] {
-    const char* e = std::getenv("FEDMI_TAP_BN");
-    return e ? std::atoi(e) : 0;
-  }();
-  if (O <= 64) return 64;
-  if (force == 64 || force == 128) return force;
-  return m_tiles * ((O + 127) / 128) < num_cus() ? 64 : 128;
-}
-static int tap_bn(const TapGeom& g) { return tap_bn_for(g.O, (g.M + 127) / 128); }
-
-// waves per conv_tap workgroup: 8 (two per SIMD, default: 8-15 % faster per conv, profiles/r5_cnn/) or 4 (one
-// per SIMD); FEDMI_TAP_WAVES overrides (A/B runs)
-static int tap_waves() {
-  static int w = [] {
-    const char* e = std::getenv("FEDMI_TAP_WAVES");
-    const int v = e ? std::atoi(e) : 8;
-    return v == 8 ? 8 : 4;
-  }();
-  return w;
-}
-
-// conv_tap reads its operands through 32-bit buffer offsets (out-of-range lanes read zeros) and keeps a
-// per-row tap-validity mask of R * S <= 64 bits
-static bool tap_fits(long in_elems, long w_elems, int R, int S) {
-  return in_elems * 2 < (1l << 31) && w_elems * 2 < (1l << 31) && R * S <= 64;
-}
-
-// Split K only to fill one wave of workgroups: conv_tap keeps 1 (BN 128, 96 KiB
-// LDS) or 2 (BN 64) workgroups per CU, and a split costs an fp32 round trip.
-// With 8-wave workgroups a half-filled chip without split-K beats split-K + combine (ResNet-18 l3 forward:
-// 24.7 vs 28.8 us, profiles/r5_cnn/): split only when the tiles fill at most a quarter of one wave of
-// workgroups.  FEDMI_TAP_SPLITS=n forces n splits where a split applies (A/B runs).
-static int tap_split_override() {
-  static int v = [] {
-    const char* e = std::getenv("FEDMI_TAP_SPLITS");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-
-static int tap_splits(const TapGeom& g, long ws_floats) {
-  if (ws_floats <= 0 || g.O > SPLITK_MAX_NC) return 1;
-  const int bn = tap_bn(g);
-  const long tiles = (long)((g.M + 127) / 128) * ((g.O + bn - 1) / bn);
-  const long target = (bn == 128 ? 1l : 2l) * num_cus();
-  const int ksteps = (g.K + 63) / 64;
-  // (a 40-step threshold saved 2.4 us on ResNet-18's layer-4 stride-2 forward but moved EfficientNetB0's
-  // 3-epoch trajectory outside its parity bound -- profiles/r5_cnn/splits/; kept at 16)
-  if (4 * tiles > target || ksteps < 16) return 1;
-  long sp = std::min<long>((target + tiles / 2) / tiles, ksteps / 8);
-  if (tap_split_override() > 0) sp = std::min<long>(tap_split_override(), ksteps / 8);
-  sp = std::min<long>(sp, ws_floats / ((long)g.M * g.O));
-  if (sp < 2) return 1;
-  const int kps = (int)((ksteps + sp - 1) / sp);
-  return (ksteps + kps - 1) / kps;
-}
-
-// halo geometry of a 3x3 / stride-1 / pad-1 problem (conv_wgrad_halo), or false
-static bool halo_geom(const TapGeom& g, const RowMap& rm, HaloGeom* h) {
-  if (rm.on || g.R != 3 || g.S != 3 || g.st != 1 || g.pad_h != 1 || g.pad_w != 1 || g.P != g.H ||
-      g.Q != g.W || g.C % 64 || g.O % 8 || g.M % 128)
-    return false;
-  const int HW = g.H * g.W;
-  HaloGeom x{};
-  x.N = g.N; x.H = g.H; x.W = g.W; x.C = g.C; x.O = g.O; x.M = g.M; x.K = 9 * g.C;
-  if (HW <= 128) {
-    if (128 % HW) return false;
-    x.IMGS = 128 / HW; x.TH = g.H;
-  } else {
-    if (128 % g.W || g.H % (128 / g.W)) return false;
-    x.IMGS = 1; x.TH = 128 / g.W;
+// FWD / DGRAD on the generic implicit GEMM; acc: out += result
+template <int MODE>
+static void issue_generic(hipStream_t st, const Gemm& l, const bf16* x, const bf16* w, const bf16* dy, bf16* out,
+                          double* stats, const float* shift, float* ws, bool acc) {
+  if (l.splits <= 1) {
+    issue_igemm<MODE>(st, l.cg, l.tile, l.tiles, l.kps, 1, x, w, dy, out, nullptr, stats, shift, acc ? 2 : 0);
+    return;
   }
-  x.PW = g.W + 2;
-  x.NPR = x.IMGS * (x.TH + 2) * x.PW;
-  x.nchunks = g.C / 64;
-  if (x.NPR > 288) return false;
-  x.dPI = make_div((x.TH + 2) * x.PW); x.dPW = make_div(x.PW); x.dTHW = make_div(x.TH * g.W);
-  x.dW = make_div(g.W); x.dHW = make_div(HW);
-  *h = x;
-  return true;
+  issue_igemm<MODE>(st, l.cg, l.tile, l.tiles, l.kps, l.splits, x, w, dy, nullptr, ws, nullptr, nullptr, 1);
+  issue_combine(st, l.M, l.NC, l.rm, ws, l.splits, out, stats, shift, acc ? out : nullptr, BnSums{});
 }
 
-static void launch_tap_reduce(hipStream_t st, const TapGeom& g, const RowMap& rm, const float* ws, int splits,
-                              bf16* out, double* stats, const float* shift, const bf16* res, const BnSums& bs) {
-  const int VR = g.O / 8;
-  const int tb = (256 / VR) * VR;
-  const int rstep = tb / VR;
-  // with BN statistics / BN-backward sums fewer blocks (their per-channel atomics contend on 2 x O addresses)
-  const int rows_per_block = (stats || bs.rep) ? std::max(2 * rstep, (g.M + 255) / 256)
-                                               : std::max(rstep, (g.M + 1023) / 1024);
-  const int nblk = (g.M + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(conv_splitk_reduce, dim3(nblk), dim3(tb), 0, st, ws, splits, g.M, g.O, rm, out, stats, shift,
-                     rows_per_block, res, bs);
-}
-
-static void launch_tap(hipStream_t st, const TapGeom& g, const bf16* in, const bf16* wt, bf16* out, double* stats,
-                       const float* shift, const RowMap& rm, float* ws, long ws_floats,
-                       const bf16* res = nullptr, const BnSums& bs = BnSums{}) {
-  if (g.C % 8 || g.C < 16 || g.O % 8) throw std::invalid_argument("conv_tap: need C % 8 == 0, C >= 16, O % 8 == 0");
-  if (!tap_fits((long)g.N * g.H * g.W * g.C, (long)g.O * g.K, g.R, g.S))
-    throw std::invalid_argument("conv_tap: operands over 2 GiB or R * S > 64");
-  const bool gen = g.C % 64 != 0;         // several taps per K step (conv_tap_body GEN)
-  const int BN = tap_bn(g);
-  const long tiles = (long)((g.M + 127) / 128) * ((g.O + BN - 1) / BN);
-  const int ksteps = (g.K + 63) / 64;
-  const int sp = tap_splits(g, ws_floats);
-  const int kps = (ksteps + sp - 1) / sp;
-  const int splits = (ksteps + kps - 1) / kps;
-  dim3 grid((unsigned)tiles, 1, (unsigned)splits);
-  float* part = splits > 1 ? ws : nullptr;
+// one conv_tap launch (GEN: several taps per K step, C % 64 != 0); a split launch leaves stats / residual / BN sums
+// to its combine
+static void issue_tap(hipStream_t st, const Gemm& l, const bf16* in, const bf16* wt, bf16* out, double* stats,
+                      const float* shift, float* ws, const bf16* res, const BnSums& bs) {
+  dim3 grid(l.tiles, 1, (unsigned)l.splits);
+  float* part = l.splits > 1 ? ws : nullptr;
   const BnSums tbs = part ? BnSums{} : bs;
   double* tst = part ? nullptr : stats;
   const bf16* trs = part ? nullptr : res;
-  if (gen) {   // 8 waves only (the default shape)
-    if (BN == 128)
-      hipLaunchKernelGGL((conv_tap<128, 8, true>), grid, dim3(512), 0, st, in, wt, out, part, tst, shift, g, rm, kps, trs,
-                         tbs);
-    else
-      hipLaunchKernelGGL((conv_tap<64, 8, true>), grid, dim3(512), 0, st, in, wt, out, part, tst, shift, g, rm, kps, trs,
-                         tbs);
-  } else if (BN == 128)
-    if (tap_waves() == 8)
-      hipLaunchKernelGGL((conv_tap<128, 8>), grid, dim3(512), 0, st, in, wt, out, part, tst, shift, g, rm, kps, trs, tbs);
-    else
-      hipLaunchKernelGGL((conv_tap<128, 4>), grid, dim3(256), 0, st, in, wt, out, part, tst, shift, g, rm, kps, trs, tbs);
-  else if (tap_waves() == 8)
-    hipLaunchKernelGGL((conv_tap<64, 8>), grid, dim3(512), 0, st, in, wt, out, part, tst, shift, g, rm, kps, trs, tbs);
+  const bool gen = l.tg.C % 64 != 0;
+  if (gen && l.tile.BN == 128)
+    hipLaunchKernelGGL((conv_tap<128, 8, true>), grid, dim3(512), 0, st, in, wt, out, part, tst, shift, l.tg, l.rm, l.kps,
+                       trs, tbs);
+  else if (gen)
+    hipLaunchKernelGGL((conv_tap<64, 8, true>), grid, dim3(512), 0, st, in, wt, out, part, tst, shift, l.tg, l.rm, l.kps,
+                       trs, tbs);
+  else if (l.tile.BN == 128)
+    hipLaunchKernelGGL((conv_tap<128, 8>), grid, dim3(512), 0, st, in, wt, out, part, tst, shift, l.tg, l.rm, l.kps, trs,
+                       tbs);
   else
-    hipLaunchKernelGGL((conv_tap<64, 4>), grid, dim3(256), 0, st, in, wt, out, part, tst, shift, g, rm, kps, trs, tbs);
-  if (splits > 1) launch_tap_reduce(st, g, rm, ws, splits, out, stats, shift, res, bs);
+    hipLaunchKernelGGL((conv_tap<64, 8>), grid, dim3(512), 0, st, in, wt, out, part, tst, shift, l.tg, l.rm, l.kps, trs,
+                       tbs);
+  if (l.splits > 1) issue_combine(st, l.M, l.NC, l.rm, ws, l.splits, out, stats, shift, res, bs);
 }
 
-// DGRAD phases as conv_tap problems over dY: (geometry, row map, image offset) per phase.
-struct TapPhase {
-  TapGeom g;
-  RowMap rm;
-  long img_off;
-  int r0, s0, nr, ns;
-  bool empty;   // no taps land on this parity (1x1 stride 2): output rows must be zero
-  int ph, pw;
-};
-
-static int dgrad_tap_phases(const ConvShape& s, TapPhase* out) {
-  int n = 0;
-  if (s.st == 1) {
-    TapPhase& t = out[n++];
-    t = TapPhase{};
-    t.g = make_tap(s.N, s.P, s.Q, s.O, s.C, s.H, s.W, s.R, s.S, 1, s.R - 1 - s.pad, s.S - 1 - s.pad);
-    t.r0 = t.s0 = 0; t.nr = s.R; t.ns = s.S;
-    return n;
-  }
-  long off = 0;
-  for (int ph = 0; ph < 2; ++ph)
-    for (int pw = 0; pw < 2; ++pw) {
-      const int r0 = (ph + s.pad) & 1, s0 = (pw + s.pad) & 1;
-      const int nr = std::max(0, (s.R - r0 + 1) / 2), ns = std::max(0, (s.S - s0 + 1) / 2);
-      const int Hp = (s.H - ph + 1) / 2, Wp = (s.W - pw + 1) / 2;
-      if (Hp <= 0 || Wp <= 0) continue;
-      TapPhase& t = out[n++];
-      t = TapPhase{};
-      t.ph = ph; t.pw = pw; t.r0 = r0; t.s0 = s0; t.nr = nr; t.ns = ns;
-      t.empty = nr * ns == 0;
-      const int d0 = (ph + s.pad - r0) / 2, e0 = (pw + s.pad - s0) / 2;
-      t.g = make_tap(s.N, s.P, s.Q, s.O, s.C, Hp, Wp, std::max(nr, 1), std::max(ns, 1), 1, nr - 1 - d0, ns - 1 - e0);
-      t.rm = make_rowmap(Hp, Wp, s.H, s.W, 2, ph, pw);
-      t.img_off = off;
-      off += (long)s.C * nr * ns * s.O;
-    }
-  return n;
-}
-
-// One-launch plan for the non-empty phases of a stride-2 DGRAD: no K split while their tiles fill the
-// chip (the phases run side by side instead of one small launch after another); otherwise split the
-// phase with the longest per-split K first (>= 8 K steps per split) until about one wave of workgroups,
-// within the workspace.  ws_need: floats the plan's split phases use.
-struct PhasePlan {
-  TapMulti tm;
-  int idx[MAX_TAP_PHASES];   // TapPhase index of each planned phase
-  int maxsp;
-  long ws_need;
-  int bn;                    // tile width of the one launch (all phases share O)
-};
-
-static PhasePlan plan_tap_phases(const TapPhase* ph, int n, long ws_cap) {
-  PhasePlan pl{};
-  TapMulti& tm = pl.tm;
-  long tiles[MAX_TAP_PHASES], total = 0;
-  int ks[MAX_TAP_PHASES];
-  long m_tiles = 0;
-  for (int i = 0; i < n; ++i)
-    if (!ph[i].empty) m_tiles += (ph[i].g.M + 127) / 128;
-  int bn = 64;
-  for (int i = 0; i < n; ++i)
-    if (!ph[i].empty) { bn = tap_bn_for(ph[i].g.O, m_tiles); break; }
-  pl.bn = bn;
-  // tap-less parities (1x1 stride 2) ride along as K = 0 phases: their tiles only write zeros (or leave an
-  // accumulated dX as it is) -- one launch instead of one zero-fill launch per empty parity
-  for (int i = 0; i < n; ++i) {
-    const int k = tm.n++;
-    pl.idx[k] = i;
-    tiles[k] = (long)((ph[i].g.M + 127) / 128) * ((ph[i].g.O + bn - 1) / bn);
-    ks[k] = ph[i].empty ? 0 : ph[i].g.K / 64;
-    tm.splits[k] = 1;
-    if (!ph[i].empty) total += tiles[k];
-  }
-  auto need = [&](const int* sp) {
-    long w = 0;
-    for (int k = 0; k < tm.n; ++k)
-      if (sp[k] > 1) w += (long)sp[k] * ph[pl.idx[k]].g.M * ph[pl.idx[k]].g.O;
-    return w;
-  };
-  const long target = (bn == 128 ? 1l : 2l) * num_cus();
-  if (4 * total < 3 * target) {
-    long wgs = total;
-    for (;;) {
-      int best = -1;
-      double bestv = 0.0;
-      for (int k = 0; k < tm.n; ++k) {
-        const double v = (double)ks[k] / tm.splits[k];
-        if (ks[k] / (tm.splits[k] + 1) >= 8 && v > bestv) { best = k; bestv = v; }
-      }
-      if (best < 0 || wgs + tiles[best] > target) break;
-      int trial[MAX_TAP_PHASES];
-      for (int k = 0; k < tm.n; ++k) trial[k] = tm.splits[k] + (k == best ? 1 : 0);
-      if (need(trial) > ws_cap) break;
-      tm.splits[best] = trial[best];
-      wgs += tiles[best];
-    }
-  }
-  long off = 0, t0 = 0;
-  pl.maxsp = 1;
-  for (int k = 0; k < tm.n; ++k) {
-    const TapPhase& q = ph[pl.idx[k]];
-    tm.kps[k] = std::max(1, (ks[k] + tm.splits[k] - 1) / tm.splits[k]);
-    tm.splits[k] = std::max(1, (ks[k] + tm.kps[k] - 1) / tm.kps[k]);
-    tm.g[k] = q.g;
-    if (q.empty) tm.g[k].K = 0;
-    tm.rm[k] = q.rm;
-    tm.woff[k] = q.img_off;
-    tm.wsoff[k] = tm.splits[k] > 1 ? off : -1;
-    if (tm.splits[k] > 1) off += (long)tm.splits[k] * q.g.M * q.g.O;
-    tm.tile0[k] = (int)t0;
-    t0 += tiles[k];
-    pl.maxsp = std::max(pl.maxsp, tm.splits[k]);
-  }
-  tm.tile0[tm.n] = (int)t0;
-  pl.ws_need = off;
-  return pl;
-}
-
-// The phases of a stride-2 DGRAD as one conv_tap_phases launch (+ one split-K combine per split phase).
-static void launch_tap_phases(hipStream_t st, const TapPhase* ph, int n, const bf16* dy, const bf16* wd, bf16* dx,
-                              float* ws, long ws_floats, const bf16* res, const BnSums& bs) {
-  const PhasePlan pl = plan_tap_phases(ph, n, ws_floats);
-  const TapMulti& tm = pl.tm;
-  if (tm.n == 0) return;
-  for (int k = 0; k < tm.n; ++k) {
-    if (tm.g[k].C % 64 || tm.g[k].O % 8 || tm.g[k].O != tm.g[0].O)
-      throw std::invalid_argument("conv_tap_phases: need C % 64 == 0, O % 8 == 0 and one O");
-    if (!tap_fits((long)tm.g[k].N * tm.g[k].H * tm.g[k].W * tm.g[k].C, (long)tm.g[k].O * tm.g[k].K, tm.g[k].R, tm.g[k].S))
-      throw std::invalid_argument("conv_tap_phases: operands over 2 GiB or R * S > 64");
-  }
-  dim3 grid((unsigned)tm.tile0[tm.n], 1, (unsigned)pl.maxsp);
-  if (pl.bn == 128)
-    if (tap_waves() == 8)
-      hipLaunchKernelGGL((conv_tap_phases<128, 8>), grid, dim3(512), 0, st, dy, wd, dx, ws, tm, res, bs);
-    else
-      hipLaunchKernelGGL((conv_tap_phases<128, 4>), grid, dim3(256), 0, st, dy, wd, dx, ws, tm, res, bs);
-  else if (tap_waves() == 8)
-    hipLaunchKernelGGL((conv_tap_phases<64, 8>), grid, dim3(512), 0, st, dy, wd, dx, ws, tm, res, bs);
-  else
-    hipLaunchKernelGGL((conv_tap_phases<64, 4>), grid, dim3(256), 0, st, dy, wd, dx, ws, tm, res, bs);
-  for (int k = 0; k < tm.n; ++k)
-    if (tm.splits[k] > 1)
-      launch_tap_reduce(st, tm.g[k], tm.rm[k], ws + tm.wsoff[k], tm.splits[k], dx, nullptr, nullptr, res, bs);
-}
-
-// FWD / DGRAD with automatic split-K through ``ws`` (null / 0 floats: never split).
-template <int MODE>
-static void launch_fd(hipStream_t st, const ConvGeom& g, const bf16* x, const bf16* w, const bf16* dy, bf16* out,
-                      double* stats, const float* shift, float* ws, long ws_floats, bool acc = false) {
-  const int sp = fd_splits(g, ws_floats);
-  if (sp <= 1) {
-    launch_mode<MODE>(st, g, x, w, dy, out, nullptr, stats, 1, shift, acc ? 2 : 0);
-    return;
-  }
-  launch_mode<MODE>(st, g, x, w, dy, nullptr, ws, nullptr, sp, nullptr, 1);
-  const int VR = g.NC / 8;
-  const int tb = (256 / VR) * VR;
-  const int rstep = tb / VR;
-  // plain combine: ~4 blocks per CU; with BN statistics fewer blocks (their
-  // per-channel atomics contend on 2 x NC addresses)
-  const int rows_per_block = stats ? std::max(2 * rstep, (g.M + 255) / 256) : std::max(rstep, (g.M + 1023) / 1024);
-  const int nblk = (g.M + rows_per_block - 1) / rows_per_block;
-  RowMap rm{};
-  if (MODE == DGRAD && g.st != 1) rm = make_rowmap(g.Hp, g.Wp, g.H, g.W, g.st, g.ph, g.pw);
-  hipLaunchKernelGGL(conv_splitk_reduce, dim3(nblk), dim3(tb), 0, st, ws, sp, g.M, g.NC, rm, out, stats, shift,
-                     rows_per_block, acc ? out : nullptr, BnSums{});
-}
-
-// K-split count for the weight gradient: at most one wave of two workgroups per CU (rounded down: ResNet-18's
-// layer-4 3x3 WGRAD, 144 tiles, 48.0 -> 40.5 us with 3 splits instead of 4 -- the fourth made a second, 64-workgroup
-// wave; profiles/r5_cnn/experiments/wgrad_splits.jsonl), at least 8 K steps per split, a bounded workspace.
-static int wgrad_splits(const ConvGeom& g, long ws_cap_floats) {
-  const TileCfg t = pick_tiles_wgrad(g.M, g.NC);
-  const long tiles = (long)((g.M + t.BM - 1) / t.BM) * ((g.NC + t.BN - 1) / t.BN);
-  const int ksteps = (g.K + BK - 1) / BK;
-  static const bool up = [] {
-    const char* e = std::getenv("FEDMI_WGRAD_SPLITS_UP");   // A/B: round 5's rounded-up count
-    return e && e[0] == '1';
-  }();
-  long sp = up ? (2l * num_cus() + tiles - 1) / tiles : std::max<long>(1, 2l * num_cus() / tiles);
-  sp = std::min<long>(sp, std::max(1, ksteps / 8));
-  if (ws_cap_floats > 0) sp = std::min<long>(sp, ws_cap_floats / ((long)g.M * g.NC));
-  sp = std::max<long>(1, sp);
-  const int kps = (int)((ksteps + sp - 1) / sp);
-  return (ksteps + kps - 1) / kps;
-}
-
-// the forward runs on conv_tap for C % 64 == 0, and (GEN) for any C % 8 == 0 from 16 channels with O % 8 == 0;
-// FEDMI_TAP_GEN=0 keeps those on the generic implicit GEMM (A/B runs, tests)
-static bool tap_gen_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("FEDMI_TAP_GEN");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-static bool fwd_tap_ok(const ConvShape& s) {
-  const long K = (long)s.R * s.S * s.C;
-  return s.O % 8 == 0 && (s.C % 64 == 0 || (tap_gen_enabled() && s.C % 8 == 0 && s.C >= 16)) &&
-         tap_fits((long)s.N * s.H * s.W * s.C, (long)s.O * K, s.R, s.S);
-}
-
-// Y[N,P,Q,O] = conv(X[N,H,W,C], W_rsc); stats (optional) += [sum | sumsq] of (Y - shift) per output channel.
 void launch_conv_fwd(hipStream_t st, const ConvShape& s, const bf16* x, const bf16* wrsc, bf16* y, double* stats,
                      const float* shift, float* ws, long ws_floats, const bf16* res) {
-  check_shape(s);
-  ConvGeom g = make_geom(s);
-  g.M = s.N * s.P * s.Q; g.NC = s.O; g.K = s.R * s.S * s.C;
-  if (fwd_tap_ok(s)) {
-    const TapGeom t = make_tap(s.N, s.H, s.W, s.C, s.O, s.P, s.Q, s.R, s.S, s.st, s.pad, s.pad);
-    launch_tap(st, t, x, wrsc, y, stats, shift, RowMap{}, ws, ws_floats, res);
+  const FdPlan p = plan_fwd(s, ws_floats, num_cus());
+  if (p.route == ROUTE_TAP || p.route == ROUTE_TAP_GEN) {
+    issue_tap(st, p.g[0], x, wrsc, y, stats, shift, ws, res, BnSums{});
     return;
   }
   if (res) throw std::invalid_argument("conv_fwd: a fused residual needs the tap path (C % 8 == 0, C >= 16)");
-  static const bool stem_on = [] {
-    const char* e = std::getenv("FEDMI_STEM");                // A/B: 0 = the generic implicit GEMM for the stem
-    return !(e && e[0] == '0');
-  }();
-  if (stem_on && s.C == 8 && s.R == 3 && s.S == 3 && s.st == 1 && s.pad == 1 && (s.O == 32 || s.O == 64)) {
-    // the network-input conv (conv_stem_kernel): ~4 pixel tiles of 16 per wave
-    const StemGeom sg{s.N, s.H, s.W, s.O, s.N * s.H * s.W};
-    const long ntiles = (sg.M + 15) / 16;
-    const unsigned nblk = (unsigned)std::max<long>(1, std::min<long>(2048, (ntiles + 15) / 16));
+  if (p.route == ROUTE_STEM) {
     if (s.O == 64)
-      hipLaunchKernelGGL(conv_stem_kernel<4>, dim3(nblk), dim3(256), 0, st, x, wrsc, y, stats, shift, sg);
+      hipLaunchKernelGGL(conv_stem_kernel<4>, dim3(p.stem_blocks), dim3(256), 0, st, x, wrsc, y, stats, shift, p.sg);
     else
-      hipLaunchKernelGGL(conv_stem_kernel<2>, dim3(nblk), dim3(256), 0, st, x, wrsc, y, stats, shift, sg);
+      hipLaunchKernelGGL(conv_stem_kernel<2>, dim3(p.stem_blocks), dim3(256), 0, st, x, wrsc, y, stats, shift, p.sg);
     return;
   }
-  launch_fd<FWD>(st, g, x, wrsc, nullptr, y, stats, shift, ws, ws_floats);
-}
-
-// dX[N,H,W,C] = conv_transpose(dY[N,P,Q,O], W_rsc)   (every element written).
-// Stride 2 runs as 4 sub-pixel phases so no MFMA multiplies a structural zero.
-// acc: dx += result (the data gradient of one branch of a multi-branch block)
-//
-// add: dx = result + add (a second incoming grad, e.g. the shortcut branch's; != dx) and bs: the
-// producer BN's backward sums taken in the epilogue -- both only on the tap path without empty
-// phases (conv_dgrad_fusable).
-// O % 64 == 0 (every stride: conv_tap / conv_tap_phases), or stride 1 with O % 8 == 0 from 16 channels: one phase, a
-// plain conv_tap problem over dY with O input channels -> conv_tap<GEN> (the GoogLeNet / zoo narrow branches)
-static bool dgrad_gen_enabled() {   // FEDMI_DGRAD_GEN=0: the GEN DGRAD only off (A/B)
-  static const bool on = [] {
-    const char* e = std::getenv("FEDMI_DGRAD_GEN");
-    return !(e && e[0] == '0');
-  }();
-  return on && tap_gen_enabled();
-}
-static bool dgrad_tap_ok(const ConvShape& s) {
-  const bool gen = s.st == 1 && dgrad_gen_enabled() && s.O % 8 == 0 && s.O >= 16;
-  return (s.O % 64 == 0 || gen) && tap_fits((long)s.N * s.P * s.Q * s.O, (long)s.C * s.R * s.S * s.O, s.R, s.S);
+  issue_generic<FWD>(st, p.g[0], x, wrsc, nullptr, y, stats, shift, ws, false);
 }
 
 int conv_dgrad_fusable(const ConvShape& s, int has_wd) {
-  check_shape(s);
-  if (!has_wd || !dgrad_tap_ok(s)) return 0;
-  TapPhase ph[4];
-  const int n = dgrad_tap_phases(s, ph);
-  for (int i = 0; i < n; ++i)
-    if (ph[i].empty) return 0;
-  return 1;
+  return plan_dgrad(s, has_wd != 0, WS_UNBOUNDED, num_cus()).fusable;
 }
 
 void launch_conv_dgrad(hipStream_t st, const ConvShape& s, const bf16* dy, const bf16* wrsc, bf16* dx, float* ws,
                        long ws_floats, const bf16* wd, int acc, const bf16* add, const BnSums* bs) {
-  check_shape(s);
-  if ((add || bs) && !conv_dgrad_fusable(s, wd != nullptr))
+  const FdPlan p = plan_dgrad(s, wd != nullptr, ws_floats, num_cus());
+  if ((add || bs) && !p.fusable)
     throw std::invalid_argument("conv_dgrad: add / BN sums need the tap path (conv_dgrad_fusable)");
   if (add && acc) throw std::invalid_argument("conv_dgrad: add and accumulate are exclusive");
   if (bs && (!bs->rep || !bs->z || !bs->mean || !bs->inv || bs->reps < 1 || (bs->zb && (!bs->meanb || !bs->invb)) ||
              (bs->msc && (bs->y || bs->msc_ld <= 0))))
     throw std::invalid_argument("conv_dgrad: incomplete BN sums descriptor");
-  if (wd != nullptr && dgrad_tap_ok(s)) {   // tap-major path on the dgrad weight image
-    TapPhase ph[4];
-    const int n = dgrad_tap_phases(s, ph);
-    if (n > 1)   // stride 2: every parity in one launch (tap-less parities as K = 0 phases that write zeros)
-      launch_tap_phases(st, ph, n, dy, wd, dx, ws, ws_floats, acc ? dx : add, bs ? *bs : BnSums{});
+  const bf16* res = acc ? dx : add;
+  const BnSums sums = bs ? *bs : BnSums{};
+  if (p.route == ROUTE_TAP_PHASES) {   // one launch + one split-K combine per split phase
+    const TapMulti& tm = p.tm;
+    dim3 grid((unsigned)tm.tile0[tm.n], 1, (unsigned)p.maxsp);
+    if (p.bn == 128)
+      hipLaunchKernelGGL((conv_tap_phases<128, 8>), grid, dim3(512), 0, st, dy, wd, dx, ws, tm, res, sums);
     else
-      launch_tap(st, ph[0].g, dy, wd + ph[0].img_off, dx, nullptr, nullptr, ph[0].rm, ws, ws_floats,
-                 acc ? dx : add, bs ? *bs : BnSums{});
-    return;
-  }
-  ConvGeom g = make_geom(s);
-  g.NC = s.C;
-  if (s.st == 1) {
-    g.M = s.N * s.H * s.W; g.K = s.R * s.S * s.O;
-    launch_fd<DGRAD>(st, g, nullptr, wrsc, dy, dx, nullptr, nullptr, ws, ws_floats, acc != 0);
-    return;
-  }
-  for (int ph = 0; ph < 2; ++ph)
-    for (int pw = 0; pw < 2; ++pw) {
-      ConvGeom q = g;
-      q.ph = ph; q.pw = pw;
-      q.r0 = (ph + s.pad) & 1; q.s0 = (pw + s.pad) & 1;
-      q.nr = std::max(0, (s.R - q.r0 + 1) / 2); q.ns = std::max(0, (s.S - q.s0 + 1) / 2);
-      q.Hp = (s.H - ph + 1) / 2; q.Wp = (s.W - pw + 1) / 2;
-      if (q.Hp <= 0 || q.Wp <= 0) continue;
-      q.dNS = make_div(std::max(q.ns, 1)); q.dWp = make_div(q.Wp); q.dHWp = make_div(q.Hp * q.Wp);
-      q.M = s.N * q.Hp * q.Wp; q.K = q.nr * q.ns * s.O;
-      if (q.K == 0) {   // phase with no taps (1x1 stride 2, odd parity): the kernel writes zeros
-        launch_mode<DGRAD>(st, q, nullptr, wrsc, dy, dx, nullptr, nullptr, 1, nullptr, acc ? 2 : 0);
-        continue;
-      }
-      launch_fd<DGRAD>(st, q, nullptr, wrsc, dy, dx, nullptr, nullptr, ws, ws_floats, acc != 0);
-    }
-}
-
-static ConvGeom wgrad_geom(const ConvShape& s) {
-  check_shape(s);
-  ConvGeom g = make_geom(s);
-  g.M = s.O; g.NC = s.R * s.S * s.C; g.K = s.N * s.P * s.Q;
-  return g;
-}
-
-// Workspace (floats) split-K FWD + DGRAD want for this shape (0: they never split).
-long conv_fd_ws_floats(const ConvShape& s) {
-  check_shape(s);
-  ConvGeom g = make_geom(s);
-  g.M = s.N * s.P * s.Q; g.NC = s.O; g.K = s.R * s.S * s.C;
-  long need = 0;
-  const long cap = 1l << 40;
-  int sp = fd_splits(g, cap);
-  if (sp > 1) need = std::max(need, (long)sp * g.M * g.NC);
-  if (fwd_tap_ok(s)) {
-    const TapGeom t = make_tap(s.N, s.H, s.W, s.C, s.O, s.P, s.Q, s.R, s.S, s.st, s.pad, s.pad);
-    const int tsp = tap_splits(t, cap);
-    if (tsp > 1) need = std::max(need, (long)tsp * t.M * t.O);
-  }
-  if (dgrad_tap_ok(s)) {
-    TapPhase ph[4];
-    const int n = dgrad_tap_phases(s, ph);
-    if (n > 1) {
-      need = std::max(need, plan_tap_phases(ph, n, cap).ws_need);
-    } else {
-      for (int i = 0; i < n; ++i) {
-        if (ph[i].empty) continue;
-        const int tsp = tap_splits(ph[i].g, cap);
-        if (tsp > 1) need = std::max(need, (long)tsp * ph[i].g.M * ph[i].g.O);
-      }
-    }
-  }
-  ConvGeom d = make_geom(s);
-  d.NC = s.C;
-  if (s.st == 1) {
-    d.M = s.N * s.H * s.W; d.K = s.R * s.S * s.O;
-    sp = fd_splits(d, cap);
-    if (sp > 1) need = std::max(need, (long)sp * d.M * d.NC);
+      hipLaunchKernelGGL((conv_tap_phases<64, 8>), grid, dim3(512), 0, st, dy, wd, dx, ws, tm, res, sums);
+    for (int k = 0; k < tm.n; ++k)
+      if (tm.splits[k] > 1)
+        issue_combine(st, tm.g[k].M, tm.g[k].O, tm.rm[k], ws + tm.wsoff[k], tm.splits[k], dx, nullptr, nullptr, res, sums);
+  } else if (p.route == ROUTE_GENERIC) {
+    for (int i = 0; i < p.n; ++i)
+      issue_generic<DGRAD>(st, p.g[i], nullptr, wrsc, dy, dx, nullptr, nullptr, ws, acc != 0);
   } else {
-    for (int ph = 0; ph < 2; ++ph) {
-      const int r0 = (ph + s.pad) & 1;
-      const int nr = std::max(0, (s.R - r0 + 1) / 2);
-      const int Hp = (s.H - ph + 1) / 2;
-      for (int pw = 0; pw < 2; ++pw) {
-        const int s0 = (pw + s.pad) & 1;
-        const int ns = std::max(0, (s.S - s0 + 1) / 2);
-        const int Wp = (s.W - pw + 1) / 2;
-        if (Hp <= 0 || Wp <= 0 || nr * ns == 0) continue;
-        ConvGeom q = d;
-        q.M = s.N * Hp * Wp; q.K = nr * ns * s.O;
-        sp = fd_splits(q, cap);
-        if (sp > 1) need = std::max(need, (long)sp * q.M * q.NC);
-      }
-    }
+    issue_tap(st, p.g[0], dy, wd + p.g[0].woff, dx, nullptr, nullptr, ws, res, sums);
   }
-  return need;
 }
 
-// conv_wgrad_halo applies to 3x3 / stride 1 / pad 1 with C and O % 64 and 128-pixel blocks; every other
-// shape takes the generic WGRAD (split-K conv_igemm).
-static bool wgrad_1x1_enabled() {   // FEDMI_WGRAD_1X1=0: 1x1 WGRADs on the generic split-K kernel (A/B)
-  static const bool on = [] {
-    const char* e = std::getenv("FEDMI_WGRAD_1X1");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-static bool wgrad_halo_geom(const ConvShape& s, HaloGeom* h, bool allow_1x1 = true) {
-  if (allow_1x1 && s.R == 1 && s.S == 1 && s.st == 1 && s.pad == 0 && s.C % 64 == 0 && s.O % 64 == 0 &&
-      wgrad_1x1_enabled()) {
-    // 1x1 / stride 1: conv_wgrad_halo<1, 1> over 128-pixel blocks (K = C marks the one-tap form).  Its 64 x 64
-    // tiles re-read each operand chunk twice as often as the generic kernel's 128 x 128 ones, which the L2 absorbs
-    // only for small problems: 1.3-2x faster at MobileNet's 16x16 / 8x8 pointwise shapes, 7-65 % slower from
-    // M * (C + O) ~ 2e7 on (GoogLeNet 32x32 256 -> 128, 16x16 512 -> 192, 8x8 832 -> 256;
-    // profiles/r6_cnn/wgrad1x1_halo/)
-    const long M = (long)s.N * s.H * s.W;
-    if (M % 128 || M >= (1l << 31) || M * (s.C + s.O) > 3l * (1l << 22)) return false;
-    HaloGeom x{};
-    x.N = s.N; x.H = s.H; x.W = s.W; x.C = s.C; x.O = s.O; x.M = (int)M; x.K = s.C;
-    x.NPR = 128; x.nchunks = s.C / 64;
-    *h = x;
-    return true;
-  }
-  if (s.R != 3 || s.S != 3 || s.st != 1 || s.pad != 1 || s.C % 64 || s.O % 64) return false;
-  const TapGeom t = make_tap(s.N, s.H, s.W, s.C, s.O, s.P, s.Q, 3, 3, 1, 1, 1);
-  // the 288-row window (4x4 images) would spill the per-lane fragment offset tables: generic path
-  return halo_geom(t, RowMap{}, h) && h->NPR <= 208;
-}
-
-// K splits of the halo WGRAD: about one workgroup per CU over the (O / 64) x (C / 64) tiles -- fewer
-// splits mean fewer fp32 partial bytes to write and reduce.
-static int wgrad_halo_splits(const HaloGeom& h, long ws_cap_floats) {
-  const long want = num_cus();
-  const long tiles = (long)(h.O / 64) * h.nchunks;
-  const int nblk = h.M / 128;
-  long sp = std::max<long>(1, (want + tiles / 2) / tiles);
-  sp = std::min<long>(sp, nblk);
-  if (ws_cap_floats > 0) sp = std::min<long>(sp, ws_cap_floats / ((long)h.O * h.K));   // K = taps * C
-  sp = std::max<long>(1, sp);
-  const int bps = (int)((nblk + sp - 1) / sp);
-  return (nblk + bps - 1) / bps;
+long conv_fd_ws_floats(const ConvShape& s) {
+  const int cus = num_cus();
+  // The engines size ONE shared workspace as the maximum of this value over their convs, and its size caps other
+  // convs' splits -- so it keeps every term it has always had: the DGRAD with and without a weight image, and the
+  // generic forward even for the shapes whose forward runs on the tap or stem route.
+  return std::max({plan_fwd(s, WS_UNBOUNDED, cus).ws_need, plan_fwd_generic(s, WS_UNBOUNDED, cus).ws_need,
+                   plan_dgrad(s, true, WS_UNBOUNDED, cus).ws_need, plan_dgrad(s, false, WS_UNBOUNDED, cus).ws_need});
 }
 
 long conv_wgrad_ws_floats(const ConvShape& s) {
-  const ConvGeom g = wgrad_geom(s);
-  long need = (long)wgrad_splits(g, 0) * g.M * g.NC;
-  HaloGeom h;
-  if (wgrad_halo_geom(s, &h)) need = std::max(need, (long)wgrad_halo_splits(h, 0) * g.M * g.NC);
-  return need;
+  const int cus = num_cus();
+  // (as above: the generic kernel's planes are counted for the shapes that run on the halo kernel too)
+  return std::max(plan_wgrad(s, WS_UNBOUNDED, 0, true, cus).ws_need, plan_wgrad_generic(s, WS_UNBOUNDED, 0, cus).ws_need);
 }
 
-// dW[O][Cw][R][S] (fp32, PyTorch layout) = (or +=) X^T dY.  ``ws`` holds
-// ws_floats floats; splits <= 0 picks automatically within that capacity.
-// dw: [Ow][Cw][R][S] (Ow <= 0: O) -- the first Ow filters of an O-padded conv land in the unpadded gradient.
-// G > 1: a grouped conv run densely with a block-diagonal weight image; filter o keeps only its group's Cw
-// channels of the dense gradient.
-// allow_1x1 = 0: no conv_wgrad_halo<1, 1> route (the aten backend: mixed results across the zoo families)
 void launch_conv_wgrad(hipStream_t st, const ConvShape& s, const bf16* x, const bf16* dy, float* dw, float* ws,
                        long ws_floats, int splits, int accumulate, int Ow, int G, WredItem* defer, int allow_1x1) {
   if (Ow <= 0 || Ow > s.O) Ow = s.O;
   if (G < 1) G = 1;
   if (G > 1 && (s.O % G || s.C < G * s.Cw || Ow != s.O))
     throw std::invalid_argument("conv_wgrad: grouped gradient needs O % G == 0, C >= G * Cw, no O pad");
-  const ConvGeom g = wgrad_geom(s);
-  const long plane = (long)g.M * g.NC;
-  if (ws_floats < plane) throw std::invalid_argument("conv_wgrad: workspace smaller than one O x RSC plane");
-  HaloGeom h;
-  if (splits <= 0 && wgrad_halo_geom(s, &h, allow_1x1 != 0)) {
-    splits = wgrad_halo_splits(h, ws_floats);
-    const int nblk = h.M / 128;
-    const int bps = (nblk + splits - 1) / splits;
-    dim3 grid((unsigned)((h.O / 64) * h.nchunks), 1, (unsigned)splits);
-    if (h.K == h.C)
-      hipLaunchKernelGGL((conv_wgrad_halo<1, 1>), grid, dim3(256), 0, st, x, dy, ws, h, bps);
-    else
-      hipLaunchKernelGGL(conv_wgrad_halo<1>, grid, dim3(256), 0, st, x, dy, ws, h, bps);
-  } else {
-    if (splits <= 0) splits = wgrad_splits(g, ws_floats);
-    const int ksteps = (g.K + BK - 1) / BK;
-    splits = std::max(1, std::min<int>(splits, ksteps));
-    const int kps = (ksteps + splits - 1) / splits;
-    splits = (ksteps + kps - 1) / kps;
-    if ((long)splits * plane > ws_floats) throw std::invalid_argument("conv_wgrad: workspace too small for splits");
-    launch_mode<WGRAD>(st, g, x, nullptr, dy, nullptr, ws, nullptr, splits);
-  }
+  const WgradPlan p = plan_wgrad(s, ws_floats, splits, allow_1x1 != 0, num_cus());
+  if (ws_floats < p.plane) throw std::invalid_argument("conv_wgrad: workspace smaller than one O x RSC plane");
+  if (p.ws_need > ws_floats) throw std::invalid_argument("conv_wgrad: workspace too small for splits");
+  dim3 grid(p.tiles, 1, (unsigned)p.splits);
+  if (p.route == ROUTE_HALO_1X1)
+    hipLaunchKernelGGL(conv_wgrad_halo<1>, grid, dim3(256), 0, st, x, dy, ws, p.h, p.kps);
+  else if (p.route == ROUTE_HALO)
+    hipLaunchKernelGGL(conv_wgrad_halo<3>, grid, dim3(256), 0, st, x, dy, ws, p.h, p.kps);
+  else
+    issue_igemm<WGRAD>(st, p.cg, p.tile, p.tiles, p.kps, p.splits, x, nullptr, dy, nullptr, ws, nullptr, nullptr, 0);
   if (s.R * s.S > WRED_MAX_RS) throw std::invalid_argument("conv_wgrad: window larger than 7x7");
-  const long blocks = (long)s.O * ((s.C + 63) / 64);
-  // enough (o, channel-block) tiles: coalesced tile writes; else one lane per workspace column
-  const WredItem it{ws, dw, blocks >= 1024 ? WRED_TILE : WRED_COLS, splits, s.O, s.C, s.Cw, s.R * s.S, accumulate, Ow, G};
+  const WredItem it{ws, dw, p.reduce_tiled ? WRED_TILE : WRED_COLS, p.splits, s.O, s.C, s.Cw, s.R * s.S, accumulate, Ow, G};
   if (defer) {               // the caller runs it later in launch_wgrad_reduce_multi
     *defer = it;
     return;
@@ -2428,14 +1811,6 @@ void launch_wgrad_reduce_multi(hipStream_t st, const WredItem* items, int n) {
   }
 }
 
-struct PackItem {
-  const float* w;
-  bf16* wr;
-  int O, Cw, C, RS;
-  int O8;            // <= 0: O (no zero filters)
-  int G;             // <= 1: dense; > 1: block-diagonal image of a grouped conv (C = G * Cw channels)
-};
-
 // All dense-conv weight images of a network from their fp32 masters, <= MAX_PACK per launch.
 void launch_conv_pack_multi(hipStream_t st, const PackItem* items, int n) {
   for (int b = 0; b < n; b += MAX_PACK) {
@@ -2457,27 +1832,23 @@ void launch_conv_pack_multi(hipStream_t st, const PackItem* items, int n) {
   }
 }
 
-// DGRAD weight images (conv_tap layout, phases concatenated) for several convs, one launch per <= MAX_DPACK phases.
-struct DPackItem {
-  const float* w;
-  bf16* wd;
-  int O, Cw, C, R, S, st, pad;
-};
+void launch_conv_pack(hipStream_t st, const float* w, bf16* wrsc, int O, int Cw, int C, int RS, int O8, int G) {
+  const PackItem it{w, wrsc, O, Cw, C, RS, O8, G};
+  launch_conv_pack_multi(st, &it, 1);
+}
 
+// One launch per <= MAX_DPACK phase images (the phases with taps, in dgrad_phases order).
 void launch_dgrad_pack_multi(hipStream_t st, const DPackItem* items, int n) {
   std::vector<DPackEntry> all;
   for (int k = 0; k < n; ++k) {
     const DPackItem& it = items[k];
     if (it.R * it.S > 49 || it.C % 8 || it.C < it.Cw) throw std::invalid_argument("dgrad_pack: unsupported shape");
-    ConvShape s{};
-    s.N = 1; s.H = 8; s.W = 8; s.P = 4; s.Q = 4;   // spatial sizes only gate empty phases here
-    s.C = it.C; s.Cw = it.Cw; s.O = it.O; s.R = it.R; s.S = it.S; s.st = it.st; s.pad = it.pad;
-    TapPhase ph[4];
-    const int np = dgrad_tap_phases(s, ph);
+    Phase ph[MAX_TAP_PHASES];
+    const int np = dgrad_phases(it.R, it.S, it.st, it.pad, ph);
     for (int i = 0; i < np; ++i) {
-      if (ph[i].empty) continue;
+      if (ph[i].nr * ph[i].ns == 0) continue;
       DPackEntry e{};
-      e.w = it.w; e.wd = it.wd + ph[i].img_off;
+      e.w = it.w; e.wd = it.wd + ph[i].tap0 * it.C * it.O;
       e.O = it.O; e.Cw = it.Cw; e.Cpad = it.C; e.R = it.R; e.S = it.S;
       e.r0 = ph[i].r0; e.s0 = ph[i].s0; e.nr = ph[i].nr; e.ns = ph[i].ns; e.step = it.st;
       all.push_back(e);
@@ -2499,19 +1870,6 @@ void launch_dgrad_pack_multi(hipStream_t st, const DPackItem* items, int n) {
   }
 }
 
-// Fused SGD + weight images (sgd_pack_kernel): the host builds the table once per engine (convs first, then the
-// flat segments, in workgroup order); the caller copies `table` to device memory and launches with it.
-struct SgdPackConv {
-  long off;          // element offset of the fp32 weight [O][Cw][R][S] in the flat master
-  bf16* wr;          // forward image [O][R][S][C] (nullptr: none)
-  bf16* wd;          // DGRAD image, phases concatenated (nullptr: none; needs O % 64 == 0)
-  int O, Cw, C, R, S, st, pad;
-};
-struct SgdPackPlan {
-  std::vector<char> table;
-  int n_entries, n_blocks, lds_bytes;
-};
-
 SgdPackPlan build_sgd_pack_plan(const SgdPackConv* convs, int nc, const long* segs, int nseg) {
   std::vector<SgdPackEntry> v;
   int blk = 0, lds = 0;
@@ -2527,14 +1885,11 @@ SgdPackPlan build_sgd_pack_plan(const SgdPackConv* convs, int nc, const long* se
     // tail, MobileNet: 16 -> 53 us, 64 -> 37, 128 -> 40; profiles/r5_cnn/sgdpack/)
     e.cb = c.R * c.S > 9 ? 4 : c.R * c.S > 4 ? DP_CB : c.R * c.S > 1 ? 32 : 64;
     if (c.wd) {
-      ConvShape s{};
-      s.N = 1; s.H = 8; s.W = 8; s.P = 4; s.Q = 4;   // spatial sizes only gate empty phases (launch_dgrad_pack_multi)
-      s.C = c.C; s.Cw = c.Cw; s.O = c.O; s.R = c.R; s.S = c.S; s.st = c.st; s.pad = c.pad;
-      TapPhase ph[4];
-      const int np = dgrad_tap_phases(s, ph);
+      Phase ph[MAX_TAP_PHASES];
+      const int np = dgrad_phases(c.R, c.S, c.st, c.pad, ph);
       for (int i = 0; i < np; ++i) {
-        if (ph[i].empty) continue;
-        e.wd[e.nph] = c.wd + ph[i].img_off;
+        if (ph[i].nr * ph[i].ns == 0) continue;
+        e.wd[e.nph] = c.wd + ph[i].tap0 * c.C * c.O;
         e.r0[e.nph] = ph[i].r0; e.s0[e.nph] = ph[i].s0; e.nr[e.nph] = ph[i].nr; e.ns[e.nph] = ph[i].ns;
         ++e.nph;
       }
@@ -2568,14 +1923,8 @@ SgdPackPlan build_sgd_pack_plan(const SgdPackConv* convs, int nc, const long* se
 void launch_sgd_pack(hipStream_t st, const void* table, int n_entries, int n_blocks, int lds_bytes, float* P,
                      const float* G, float* B, float lr, float m, float wd, float dampening, int nesterov, int first) {
   if (n_entries <= 0 || n_blocks <= 0) return;
-  hipLaunchKernelGGL(sgd_pack_kernel<4>, dim3((unsigned)n_blocks), dim3(256), lds_bytes, st,
+  hipLaunchKernelGGL(sgd_pack_kernel, dim3((unsigned)n_blocks), dim3(256), lds_bytes, st,
                      static_cast<const SgdPackEntry*>(table), n_entries, P, G, B, lr, m, wd, dampening, nesterov, first);
-}
-
-
-void launch_conv_pack(hipStream_t st, const float* w, bf16* wrsc, int O, int Cw, int C, int RS, int O8, int G) {
-  const PackItem it{w, wrsc, O, Cw, C, RS, O8, G};
-  launch_conv_pack_multi(st, &it, 1);
 }
 
 }  // namespace fedmi

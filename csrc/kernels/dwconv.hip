@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <stdexcept>
 
+#include "cnn_ops.h"
 #include "common.h"
 #include "wgrad_reduce.h"
 
@@ -598,10 +599,6 @@ int block_threads(int C) { const int vc = C / 8; return (256 / vc) * vc; }
 }  // namespace
 
 namespace fedmi {
-
-struct DwShape {
-  int N, H, W, C, R, S, st, pad;
-};
 
 static DwGeom dw_geom(const DwShape& s) {
   if (s.C % 8 || s.C / 8 > 256) throw std::invalid_argument("dwconv: need C % 8 == 0 and C <= 2048");

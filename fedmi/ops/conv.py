@@ -12,7 +12,6 @@ Reference ops: ``convolution`` / ``convolution_backward`` of every zoo model
 """
 from __future__ import annotations
 
-import os
 from typing import Optional, Tuple
 
 import torch
@@ -147,17 +146,12 @@ def dgrad_image_numel(w_shape, c_pad: Optional[int] = None) -> int:
     return O * R * S * (c_pad or pad8(Cw))
 
 
-# FEDMI_TAP_GEN=0: convs with C % 64 != 0 (forward) / O % 64 != 0 (stride-1 DGRAD) stay on the generic implicit
-# GEMM (conv_igemm.hip tap_gen_enabled; A/B runs)
-TAP_GEN = os.environ.get("FEDMI_TAP_GEN", "1") != "0"
-DGRAD_GEN = TAP_GEN and os.environ.get("FEDMI_DGRAD_GEN", "1") != "0"     # the stride-1 GEN DGRAD only (A/B)
-
-
 def dgrad_eligible(O: int, stride: Optional[int] = None) -> bool:
     """The tap-major DGRAD reads dY as its input operand (O input channels): O % 64 == 0, or, at stride 1 (one
     phase: a plain conv_tap problem), any O % 8 == 0 from 16 channels on ``conv_tap<GEN>`` (several taps per K
-    step).  ``stride`` None: the stride-independent condition."""
-    return O % 64 == 0 or (stride == 1 and DGRAD_GEN and O % 8 == 0 and O >= 16)
+    step).  ``stride`` None: the stride-independent condition.  Mirrors ``dgrad_tap_ok`` of csrc/kernels/conv_plan.h
+    (tests/test_conv_dispatch.py holds the two together)."""
+    return O % 64 == 0 or (stride == 1 and O % 8 == 0 and O >= 16)
 
 
 def dgrad_pack_weights(items) -> None:
@@ -320,9 +314,8 @@ def wgrad_ws_floats(x_shape, O: int, R: int, S: int, stride: int, pad: int, Cw: 
     return int(native.require().conv_wgrad_ws_floats(shape_tuple(x_shape, O, R, S, stride, pad, Cw)))
 
 
-# Pixel count (N*H*W) up to which a 1x1 / stride-1 WGRAD goes to the library GEMM; FEDMI_WGRAD_GEMM=0 keeps every
-# WGRAD native (A/B switch).
-WGRAD_GEMM_PIXELS = 2048 if os.environ.get("FEDMI_WGRAD_GEMM", "1") != "0" else 0
+# Pixel count (N*H*W) up to which a 1x1 / stride-1 WGRAD goes to the library GEMM (0: every WGRAD native).
+WGRAD_GEMM_PIXELS = 2048
 
 
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int, pad: int, Cw: Optional[int] = None,

@@ -27,6 +27,9 @@ SHAPES = [
     (4, 32, 32, 192, 16, 1, 1, 0),     # a3 1x1 -> 16 (K = 16: one masked K step)
     (4, 32, 32, 16, 32, 3, 1, 1),      # a3 16 -> 32 3x3
     (4, 8, 8, 832, 48, 1, 1, 0),       # b5 1x1 -> 48
+    # C = 8 off the stem pattern: the only forwards left on the generic implicit GEMM
+    (8, 8, 8, 8, 16, 3, 2, 1),
+    (2, 8, 8, 8, 24, 1, 1, 0),
 ]
 
 
@@ -150,7 +153,7 @@ def test_conv_wgrad_1x1_library_route(gpu_device, shape, monkeypatch):
 @pytest.mark.parametrize("shape", [(8, 16, 16, 64, 128), (4, 32, 32, 192, 64), (16, 8, 8, 256, 256), (2, 8, 8, 128, 64),
                                    (128, 8, 8, 832, 256)])
 def test_conv_wgrad_1x1_halo_kernel(gpu_device, shape, monkeypatch):
-    """1x1 / stride-1 WGRAD with C, O % 64 (M (C + O) <= 12.6 M) runs on conv_wgrad_halo<1, 1> (the block's own
+    """1x1 / stride-1 WGRAD with C, O % 64 (M (C + O) <= 12.6 M) runs on conv_wgrad_halo<1> (the block's own
     pixel rows as the one-tap patch); against fp32 and the generic kernel (explicit splits, and lib_gemm=False --
     the aten backend's route -- both take it)."""
     N, H, W, C, O = shape
@@ -434,6 +437,35 @@ def test_conv_splitk_fwd_dgrad(gpu_device, shape):
     dx2 = conv.conv2d_dgrad(dyn, wr, xn.shape, st, pad, Cw=Cw, ws=ws, wd=wd)
     torch.cuda.synchronize()
     assert _rel(dx2.float(), _nhwc(xr.grad)) < 1e-2
+
+
+SMALL_SPLIT_SHAPES = [(16, 4, 4, 512, 512, 3, 1, 1), (8, 8, 8, 256, 512, 3, 2, 1), (16, 4, 4, 160, 320, 3, 1, 1)]
+
+
+@pytest.mark.parametrize("shape", SMALL_SPLIT_SHAPES, ids=[str(s) for s in SMALL_SPLIT_SHAPES])
+def test_conv_splitk_plan_does_not_depend_on_spare_workspace(gpu_device, shape):
+    """A workspace of exactly fd_ws_floats and one four times larger plan the same splits (the engines size one
+    shared workspace as the maximum over their convs): forward with statistics and tap DGRAD are bitwise equal."""
+    N, H, W, Cw, O, R, st, pad = shape
+    x, w, wb, xn = _make(shape, gpu_device, seed=6)
+    wr = conv.pack_weight(w)
+    need = conv.fd_ws_floats(xn.shape, O, R, R, st, pad, Cw)
+    assert need > 0, "shape expected to take the split-K path"
+    shift = torch.randn(O, device=gpu_device) * 0.1
+    dy = torch.randn(N, *conv.out_hw(H, W, R, R, st, pad), O, device=gpu_device).bfloat16()
+    wd = torch.empty(conv.dgrad_image_numel(w.shape, xn.shape[-1]), dtype=torch.bfloat16, device=gpu_device)
+    conv.dgrad_pack_weights([(w, wd, st, pad, xn.shape[-1])])
+    got = []
+    for floats in (need, 4 * need):
+        ws = torch.full((floats,), float("nan"), device=gpu_device)
+        stats = conv.stats_buffer(O, gpu_device)
+        y = conv.conv2d_fwd(xn, wr, st, pad, Cw=Cw, stats=stats, shift=shift, ws=ws)
+        dx = conv.conv2d_dgrad(dy, wr, xn.shape, st, pad, Cw=Cw, ws=ws, wd=wd)
+        torch.cuda.synchronize()
+        got.append((y, conv.stats_total(stats), dx))
+    assert torch.isfinite(got[0][0].float()).all() and torch.isfinite(got[0][2].float()).all()
+    for a, b in zip(*got):
+        assert torch.equal(a, b)
 
 
 def test_conv_wgrad_many_splits_and_padded_channels(gpu_device):

@@ -1,12 +1,12 @@
 """Probe: 1x1 / stride-1 WGRAD per shape (batch 128, C and O % 64), graph-replayed µs per call (WGRAD + reduce) of
-whatever route the launcher takes -- run twice, with FEDMI_WGRAD_1X1=0 (generic split-K conv_igemm) and =1
-(conv_wgrad_halo<1, 1>), to pick the shapes the one-tap halo kernel should take.  ``--lib`` keeps the library GEMM
-route of <= 2048-pixel problems (MobileNet's 4x4 / 2x2 pointwise convs) for the halo-vs-library comparison.
+the route the launcher takes -- run twice, with ``--generic`` (``lib_gemm=False``: the generic split-K conv_igemm)
+and without (conv_wgrad_halo<1> where it applies), to pick the shapes the one-tap halo kernel should take.  ``--lib``
+keeps the library GEMM route of <= 2048-pixel problems (MobileNet's 4x4 / 2x2 pointwise convs) for the
+halo-vs-library comparison.
 
-    FEDMI_WGRAD_1X1=1 python tools/probes/wgrad1x1_halo_probe.py [--lib]
+    python tools/probes/wgrad1x1_halo_probe.py [--generic] [--lib]
 """
 import json
-import os
 import sys
 from pathlib import Path
 
@@ -27,7 +27,7 @@ SHAPES = [(16, 64, 128), (16, 128, 128), (8, 128, 256), (8, 256, 256),
 
 def main():
     dev = torch.device("cuda:0")
-    mode = os.environ.get("FEDMI_WGRAD_1X1", "1")
+    generic = "--generic" in sys.argv
     lib = "--lib" in sys.argv
     if not lib:
         conv.WGRAD_GEMM_PIXELS = 0      # CNN-engine routing (lib_gemm=True) minus the small-M library GEMM
@@ -41,8 +41,8 @@ def main():
         dw = torch.empty(O, C, 1, 1, device=dev)
 
         def run():
-            conv.conv2d_wgrad(x, dy, 1, 1, 1, 0, out=dw, ws=ws)
-        print(json.dumps({"H": H, "C": C, "O": O, "halo1": mode, "lib": lib, "us": round(timed(run), 2),
+            conv.conv2d_wgrad(x, dy, 1, 1, 1, 0, out=dw, ws=ws, lib_gemm=not generic)
+        print(json.dumps({"H": H, "C": C, "O": O, "halo1": "0" if generic else "1", "lib": lib, "us": round(timed(run), 2),
                           "splits": ws.numel() // (O * C)}), flush=True)
 
 
