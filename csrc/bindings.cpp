@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <vector>
 
 #include "kernels/common.h"
@@ -30,6 +31,8 @@ void launch_server_opt(hipStream_t, float*, float*, float*, float*, long, long, 
 void launch_drift_grad(hipStream_t, int, float*, const float*, const float*, const float*, float*, float, long);
 void launch_scaffold_finish(hipStream_t, const float*, float*, float*, long, long);
 void launch_scaffold_begin(hipStream_t, float*, const float*, const float*, float*, float*, long);
+int dp_partials(long);
+void launch_dp(hipStream_t, float*, const float*, long, double*, double*, double, float, uint64_t, uint64_t, int);
 void launch_ef_delta(hipStream_t, const float*, const float*, const float*, float*, long);
 size_t topk_state_bytes();
 size_t topk_overflow_offset();
@@ -171,6 +174,33 @@ static void fedmi_bind(py::module_& m) {
     check_last("server_opt");
   }, py::arg("stream"), py::arg("x"), py::arg("anchor"), py::arg("m"), py::arg("v"), py::arg("n"), py::arg("n_opt"),
      py::arg("kind"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("tau"));
+
+  // differentially private FedAvg on the client's update x - anchor over the k trainable entries of the n-entry
+  // float state: dp_sumsq, dp_finish and the clip (+ noise when z > 0) apply, stream-ordered with no host sync.
+  // partial: dp_partials(k) doubles of scratch; stats: {sumsq, norm, scale} as three doubles.  sigma =
+  // (float)(z * clip / sqrt(world)).  stages selects the launches (1 | 2 | 4; the round runs all three).
+  m.def("dp_partials", [](long k) {
+    if (k < 0) throw std::invalid_argument("dp_partials: need k >= 0");
+    return dp_partials(k);
+  });
+  m.def("dp_privatize", [](uintptr_t st, uintptr_t x, uintptr_t anchor, long n, long k, uintptr_t partial,
+                           uintptr_t stats, double clip, double z, int world, uint64_t key, uint64_t draw, int stages) {
+    if (n < 0 || k < 0 || k > n) throw std::invalid_argument("dp_privatize: need 0 <= k <= n");
+    if (!(clip > 0.0) || !std::isfinite(clip)) throw std::invalid_argument("dp_privatize: need a finite clip norm S > 0");
+    if (!(z >= 0.0) || !std::isfinite(z)) throw std::invalid_argument("dp_privatize: need a finite noise multiplier z >= 0");
+    if (world < 1) throw std::invalid_argument("dp_privatize: need world >= 1");
+    if (stages < 1 || stages > 7) throw std::invalid_argument("dp_privatize: stages must be in 1..7");
+    if (k == 0) return;
+    if (!x || !anchor || !partial || !stats) throw std::invalid_argument("dp_privatize: null buffer");
+    if ((x | anchor) % 16) throw std::invalid_argument("dp_privatize: x and anchor must be 16-byte aligned");
+    if ((partial | stats) % 8) throw std::invalid_argument("dp_privatize: partial and stats must be 8-byte aligned");
+    const float sigma = (float)(z * clip / std::sqrt((double)world));
+    launch_dp(S(st), P<float>(x), P<const float>(anchor), k, P<double>(partial), P<double>(stats), clip, sigma, key,
+              draw, stages);
+    check_last("dp_privatize");
+  }, py::arg("stream"), py::arg("x"), py::arg("anchor"), py::arg("n"), py::arg("k"), py::arg("partial"),
+     py::arg("stats"), py::arg("clip"), py::arg("z"), py::arg("world"), py::arg("key"), py::arg("draw"),
+     py::arg("stages") = 7);
 
   // client-side drift correction of the flat gradient, between the backward pass and the SGD tail (kind: 0
   // fedprox -- g, p, anchor, mu; 1 scaffold -- g, corr, acc); the other kind's buffers may be 0

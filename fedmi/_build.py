@@ -29,6 +29,7 @@ SOURCES = [
     CSRC / "kernels" / "flat_ops.hip",
     CSRC / "kernels" / "server_opt.hip",
     CSRC / "kernels" / "client_opt.hip",
+    CSRC / "kernels" / "dp.hip",
     CSRC / "kernels" / "compress.hip",
     CSRC / "kernels" / "conv_igemm.hip",
     CSRC / "kernels" / "cnn_ops.hip",

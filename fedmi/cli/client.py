@@ -21,6 +21,7 @@ from ..engine.base import TrainerConfig
 from ..engine.data import label_shard_indices, make_dataset
 from ..parallel.client_opt import add_client_opt_flags, make_client_opt
 from ..parallel.compress import make_compressor
+from ..parallel.dp import add_dp_flags, check_dp_flags, make_dp
 from ..parallel.fedavg import FedAvg
 from ..parallel.group import GroupManager
 from ..parallel.server_opt import add_server_opt_flags, make_server_opt
@@ -64,6 +65,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--compress-warmup", type=int, default=0, help="dense FedAvg rounds before -c Y compression starts")
     add_server_opt_flags(ap)
     add_client_opt_flags(ap)
+    add_dp_flags(ap)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--root", default=".")
     ap.add_argument("--metrics", default=None)
@@ -89,6 +91,7 @@ def main(argv=None) -> int:
                  "(reference peers), nothing carries scaffold's control variate or re-anchors fedprox")
     if a.client_mu < 0:
         ap.error("--client-mu must be >= 0")
+    check_dp_flags(a, ap.error)
     gzip = a.compressFlag == "Y"
     dev = pick_device(a.device)
     if dev.type == "cuda":
@@ -113,6 +116,7 @@ def main(argv=None) -> int:
                     if a.model.lower() == "lenet" else ""))
     fedavg = FedAvg(compressor=make_compressor(comp_kind, a.topk_ratio, trainer, a.compress_warmup),
                     client_opt=client_opt,
+                    dp=make_dp(a.dp_clip, trainer, a.dp_noise, a.dp_delta, a.dp_seed, who=a.address),
                     server_opt=make_server_opt(a.server_opt, trainer, a.server_lr, a.server_beta1, a.server_beta2,
                                                a.server_tau))
     n = trainer.float_state().numel()

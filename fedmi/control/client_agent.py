@@ -347,6 +347,9 @@ class ClientAgent(P.TrainerServicer):
                 self._void_round(rnd, gen, err, context, lease_stats)
             rec["eval_ms"] = t3.ms()
             rec.update(ev.as_dict("test"))
+            dp = getattr(self.fedavg, "dp", None)
+            if dp is not None:
+                rec.update(dp.round_stats())    # update norm, clip scale, epsilon so far: no sync of its own
             self.round = rnd
             self._check_compressor(rnd)
             t4 = Timer()

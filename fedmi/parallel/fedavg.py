@@ -100,6 +100,7 @@ class FedAvg:
     abort: Optional[threading.Event] = None  # the generation's loss flag (GroupManager.abort_event)
     server_opt: Optional[object] = None      # fedmi.parallel.server_opt.ServerOpt (None: plain FedAvg)
     client_opt: Optional[object] = None      # fedmi.parallel.client_opt.ClientOpt (None: plain local SGD)
+    dp: Optional[object] = None              # fedmi.parallel.dp.DpGuard (None: the raw update is aggregated)
 
     def world(self) -> int:
         if self.transport is not None:
@@ -122,8 +123,8 @@ class FedAvg:
         return base
 
     def opts(self) -> list:
-        """The attached optimizers (:class:`fedmi.parallel.replicated.ReplicatedState`): server, then client."""
-        return [o for o in (self.server_opt, self.client_opt) if o is not None]
+        """The attached :class:`fedmi.parallel.replicated.ReplicatedState`: server and client optimizer, DP guard."""
+        return [o for o in (self.server_opt, self.client_opt, self.dp) if o is not None]
 
     def snapshot_opts(self) -> None:
         for o in self.opts():
@@ -149,6 +150,10 @@ class FedAvg:
         co = self.client_opt
         if co is not None:
             co.finish_round()                 # scaffold: c_i = the epoch's mean raw gradient, delta = its change
+        if self.dp is not None:
+            # the client's update is clipped (and noised) before anything leaves it; the compressor, the mean and
+            # the server step below see the privatised model only (post-processing).  At world 1: its own update.
+            self.dp.privatize(trainer, self.world())
         if self.world() > 1:
             if self.compressor is not None:
                 self.compressor.aggregate(trainer, self.group, transport=self.transport)
@@ -175,6 +180,8 @@ class FedAvg:
             # float_state() is the next round's starting model (fedprox anchor); at world 1 the client's own
             # delta is the mean
             co.begin_round(trainer, co.delta)
+        if self.dp is not None:
+            self.dp.begin_round(trainer)      # the next round's update is measured from this model
         trainer.after_aggregate()
         dt = (time.perf_counter() - t0) * 1e3
         self.timer.last_ms = dt

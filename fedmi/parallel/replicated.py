@@ -2,7 +2,8 @@
 
 A server optimizer (:mod:`.server_opt`) and a client optimizer (:mod:`.client_opt`) both hold tensors that every
 client must compute to the same bits without a server, and FedAvg and the client agent ask the same of either (the
-classes below).  The compressors (:mod:`.compress`) stay outside: they have no snapshot and nothing of theirs is
+classes below).  The DP guard (:mod:`.dp`) uses the same contract for its anchor and its settings check; its key and
+draw counter are per client and deliberately outside it.  The compressors (:mod:`.compress`) stay outside: they have no snapshot and nothing of theirs is
 handed over.
 """
 from __future__ import annotations
@@ -40,7 +41,7 @@ class ReplicatedConfig:
 
 
 class ReplicatedState:
-    """Base of ``ServerOpt`` and ``ClientOpt``, built from the trainer's flat float state ``x`` (it decides the
+    """Base of ``ServerOpt``, ``ClientOpt`` and ``DpGuard``, built from the trainer's flat float state ``x`` (it decides the
     device and whether the HIP kernels run).  A subclass says in ``_rolled()`` which tensors a void round must
     restore and in ``_after_rollback()`` what else it must undo, and adds ``state_tensors()`` (what a joining
     client receives from the survivors) and ``reset(trainer)`` (re-anchor on a model installed from outside)."""

@@ -55,6 +55,7 @@ def _run_seed(a, seed, data, dev, out) -> None:
     from fedmi.engine.base import TrainerConfig
     from fedmi.engine.data import contiguous_schedule, label_shard_indices, strided_schedule
     from fedmi.parallel.client_opt import make_client_opt
+    from fedmi.parallel.dp import make_dp
     from fedmi.parallel.server_opt import make_server_opt
 
     cfg = TrainerConfig(seed=seed, lr=a.lr, augment=not a.no_augment, use_graph=not a.no_graph)
@@ -83,6 +84,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
     # one client optimizer per simulated client (its own c_i / anchor); the mean of their delta stands in for
     # the second all-reduce
     copts = [make_client_opt(a.client_opt, tr, a.client_mu) for tr in clients]
+    # one DP guard per simulated client: its own key, anchor and draw counter; each adds its 1/sqrt(W) noise share
+    dps = [make_dp(a.dp_clip, tr, a.dp_noise, a.dp_delta, a.dp_seed, who=f"seed{seed}/client{r}")
+           for r, tr in enumerate(clients)]
     for rnd in range(1, a.rounds + 1):
         t0 = time.perf_counter()
         tstats = []
@@ -96,6 +100,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
                     co.finish_round()
                 if copts[0].delta is not None:
                     dmean = torch.stack([co.delta for co in copts]).mean(0)
+            for tr, dp in zip(clients, dps):
+                if dp is not None:
+                    dp.privatize(tr, W)
             mean = torch.stack([tr.float_state() for tr in clients]).mean(0)
             ints = [torch.div(sum(bs), W, rounding_mode="floor")
                     for bs in zip(*[[b.clone() for b in tr.int_state()] for tr in clients])]
@@ -111,6 +118,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
             for tr, co in zip(clients, copts):
                 if co is not None:
                     co.begin_round(tr, dmean)
+            for tr, dp in zip(clients, dps):
+                if dp is not None:
+                    dp.begin_round(tr)
         if a.bn_eval == "batch":
             _eval_batch_bn(clients[0])
         else:
@@ -127,6 +137,12 @@ def _run_seed(a, seed, data, dev, out) -> None:
                "train_loss": [round(s.loss, 4) for s in tstats], "train_acc": [round(s.acc, 2) for s in tstats],
                "test_loss": round(ev.loss, 4), "test_acc": round(ev.acc, 2),
                "finite": bool(torch.isfinite(mean).all()), "round_s": round(time.perf_counter() - t0, 3)}
+        if dps[0] is not None:
+            # the eval above synchronised, so every client's stats row of this round is on the host
+            rows = [dp.round_stats() for dp in dps]
+            rec.update(dp_clip=a.dp_clip, dp_noise=a.dp_noise, dp_delta=a.dp_delta, dp_epsilon=rows[0]["dp_epsilon"],
+                       dp_norm=[round(r.get("dp_norm", -1.0), 4) for r in rows],
+                       dp_scale=[round(r.get("dp_scale", -1.0), 4) for r in rows])
         line = json.dumps(rec)
         print(line, flush=True)
         if out:
@@ -134,7 +150,7 @@ def _run_seed(a, seed, data, dev, out) -> None:
             out.flush()
 
 
-def main() -> int:
+def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--model", default="resnet18")
     ap.add_argument("--clients", type=int, default=2)
@@ -163,9 +179,13 @@ def main() -> int:
     from fedmi.parallel.client_opt import add_client_opt_flags
 
     add_client_opt_flags(ap)
-    a = ap.parse_args()
+    from fedmi.parallel.dp import add_dp_flags, check_dp_flags
+
+    add_dp_flags(ap)
+    a = ap.parse_args(argv)
     if a.client_mu < 0:
         ap.error("--client-mu must be >= 0")
+    check_dp_flags(a, ap.error)
     if a.bn_eval == "batch" and a.engine == "native":
         ap.error("--bn-eval batch needs a PyTorch engine (fp32 / bf16)")
     if a.engine in ("fp32", "bf16"):
