@@ -243,26 +243,41 @@ static void fedmi_bind(py::module_& m) {
                       uintptr_t cidx, uintptr_t ckey, uintptr_t idx, uintptr_t val) {
     if (k <= 0 || k > n) throw std::invalid_argument("topk_ef: need 0 < k <= n");
     if (n >= (1L << 30)) throw std::invalid_argument("topk_ef: n must be < 2^30 (int32 indices, 2n scratch)");
+    if (!x || !g || !residual || !state || !cidx || !ckey || !idx || !val) throw std::invalid_argument("topk_ef: null buffer");
     launch_topk_ef(S(st), P<const float>(x), P<const float>(g), P<float>(residual), n, k, P<void>(state), P<int>(cidx),
                    P<unsigned>(ckey), P<int>(idx), P<float>(val));
     check_last("topk_ef");
   }, py::arg("stream"), py::arg("x"), py::arg("g"), py::arg("residual"), py::arg("n"), py::arg("k"), py::arg("state"),
      py::arg("cidx"), py::arg("ckey"), py::arg("idx"), py::arg("val"));
+  // the four below: n (m) < 0, R <= 0 or a null required buffer is an error; n == 0 (m == 0) returns without a launch
   m.def("ef_delta", [](uintptr_t st, uintptr_t local, uintptr_t global, uintptr_t residual, uintptr_t d, long n) {
+    if (n < 0) throw std::invalid_argument("ef_delta: need n >= 0");
+    if (n == 0) return;
+    if (!local || !global || !d) throw std::invalid_argument("ef_delta: null buffer (only residual may be 0)");
     launch_ef_delta(S(st), P<const float>(local), P<const float>(global), P<const float>(residual), P<float>(d), n);
     check_last("ef_delta");
   });
   m.def("scatter_add_ranked", [](uintptr_t st, uintptr_t out, uintptr_t idx, uintptr_t val, int R, long m_, float scale,
                                  long n) {
     if (R <= 0) throw std::invalid_argument("scatter_add_ranked: R must be > 0");
+    if (m_ < 0 || n < 0) throw std::invalid_argument("scatter_add_ranked: need m >= 0 and n >= 0");
+    if (m_ == 0 || n == 0) return;
+    if (!out || !idx || !val) throw std::invalid_argument("scatter_add_ranked: null buffer");
     launch_scatter_add_ranked(S(st), P<float>(out), P<const int>(idx), P<const float>(val), R, m_, scale, n);
     check_last("scatter_add_ranked");
   });
   m.def("quant_int8", [](uintptr_t st, uintptr_t d, long n, uintptr_t q, uintptr_t scales, uintptr_t residual) {
+    if (n < 0) throw std::invalid_argument("quant_int8: need n >= 0");
+    if (n == 0) return;
+    if (!d || !q || !scales) throw std::invalid_argument("quant_int8: null buffer (only residual may be 0)");
     launch_quant_int8(S(st), P<const float>(d), n, P<signed char>(q), P<float>(scales), P<float>(residual));
     check_last("quant_int8");
   });
   m.def("dequant_accum", [](uintptr_t st, uintptr_t q, uintptr_t scales, int R, long n, uintptr_t out, float scale) {
+    if (R <= 0) throw std::invalid_argument("dequant_accum: R must be > 0");
+    if (n < 0) throw std::invalid_argument("dequant_accum: need n >= 0");
+    if (n == 0) return;
+    if (!q || !scales || !out) throw std::invalid_argument("dequant_accum: null buffer");
     launch_dequant_accum(S(st), P<const signed char>(q), P<const float>(scales), R, n, P<float>(out), scale);
     check_last("dequant_accum");
   });

@@ -223,9 +223,10 @@ __global__ __launch_bounds__(256) void peer_allgather_kernel(PeerArgs a, const u
 // 16-byte loads / stores, the chunk's absmax by wave shuffles only -- no workgroup barrier per chunk); block b's
 // waves take chunks 4b + w, 4b + w + 4G, ... on every rank.  Phase 1: d = x - g + r, scale s = absmax / 127,
 // q = rint(d / s) clamped to +-127, r <- d - q * s; q (int8) and s go to this rank's staging slot.  Peer barrier of
-// block b.  Phase 2, same chunks: acc = sum over ranks 0..W-1 of q_p * s_p, g += scale * acc, x = g.  The formulas
-// and the summation order are those of ef_delta / quant_int8 / dequant_accum (compress.hip), so the result is
-// bit-identical to the unfused path and to every other rank.  Staging: q bytes [0, n16), scales (fp32) from n16.
+// block b.  Phase 2, same chunks: acc = sum over ranks 0..W-1 of q_p * s_p, g += scale * acc, x = g.  Every value
+// is the single explicitly rounded operation listed under "Roundings" in the header comment of compress.hip (the
+// formulas and the summation order of ef_delta / quant_int8 / dequant_accum), so the result is bit-identical to
+// the unfused path and to every other rank.  Staging: q bytes [0, n16), scales (fp32) from n16.
 // x, g, r: 16-byte aligned (the host checks); the tail chunk's lanes past n go element by element.
 PDEV void i8_load4(const float* p, long long i, long long n, float v[4]) {
   if (i + 3 < n) {
@@ -264,18 +265,19 @@ __global__ __launch_bounds__(256) void peer_int8_ef_kernel(PeerArgs a, float* __
     float am = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      v[e] = i + e < n ? (xv[e] - gv[e]) + rv[e] : 0.f;
+      v[e] = i + e < n ? __fadd_rn(__fsub_rn(xv[e], gv[e]), rv[e]) : 0.f;
       am = fmaxf(am, fabsf(v[e]));
     }
     for (int off = 32; off > 0; off >>= 1) am = fmaxf(am, __shfl_xor(am, off, 64));
-    const float sc = am > 0.f ? am / 127.f : 1.f;
+    const float t127 = __fdiv_rn(am, 127.f);
+    const float sc = t127 > 0.f ? t127 : 1.f;
     uint32_t packed = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float rq = rintf(v[e] / sc);
+      const float rq = rintf(__fdiv_rn(v[e], sc));
       const int qi = (int)fminf(fmaxf(rq, -127.f), 127.f);
       packed |= (uint32_t)(qi & 0xff) << (8 * e);
-      rv[e] = v[e] - (float)qi * sc;
+      rv[e] = __fmaf_rn(-(float)qi, sc, v[e]);
     }
     i8_store4(r, i, n, rv);
     if (i < n16) *reinterpret_cast<uint32_t*>(mine + i) = packed;     // (n16 % 4 == 0: whole words)
@@ -291,12 +293,12 @@ __global__ __launch_bounds__(256) void peer_int8_ef_kernel(PeerArgs a, float* __
       const uint32_t qw = *reinterpret_cast<const uint32_t*>(base + i);
       const float sp = reinterpret_cast<const float*>(base + n16)[c];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] += (float)(signed char)((qw >> (8 * e)) & 0xff) * sp;
+      for (int e = 0; e < 4; ++e) acc[e] = __fmaf_rn((float)(signed char)((qw >> (8 * e)) & 0xff), sp, acc[e]);
     }
     float gv[4];
     i8_load4(g, i, n, gv);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) gv[e] = gv[e] + scale * acc[e];
+    for (int e = 0; e < 4; ++e) gv[e] = __fmaf_rn(scale, acc[e], gv[e]);
     i8_store4(g, i, n, gv);
     i8_store4(x, i, n, gv);
   }

@@ -15,6 +15,21 @@
 //
 // The compressed payloads are all-gathered over RCCL and folded back with
 // scatter_add_ranked (rank-ordered, atomic-free) / dequant_accum.
+//
+// Roundings.  Every fp32 value these kernels (and peer_int8_ef_kernel, csrc/comm/peer_comm.hip, and the CPU twin
+// in fedmi/parallel/compress.py) produce is ONE explicitly written correctly rounded operation, so the bits do
+// not depend on what the compiler contracts and the fused and unfused paths agree by construction
+// (tests/int8_check.py is the exact reference):
+//
+//   delta       d   = (x - g) + r                          two roundings, no fma (r = 0 without a residual)
+//   scale       t   = __fdiv_rn(amax, 127);  s = t > 0 ? t : 1     amax = max |d| over the 256-entry chunk; a
+//                                                          subnormal amax whose quotient underflows to 0 is
+//                                                          treated like an all-zero chunk (q = 0, residual = d)
+//   quantise    q   = clamp(rintf(__fdiv_rn(v, s)), +-127)
+//   residual    r   = __fmaf_rn(-(float)q, s, v)
+//   accumulate  acc = __fmaf_rn((float)q_p, s_p, acc)      over ranks p = 0..W-1 in order, acc starts at 0
+//   apply       out = __fmaf_rn(scale, acc, out)           dequant_accum and the fused kernel's g
+//   scatter     out[j] = __fmaf_rn(scale, val, out[j])     ranks one after another, in order
 #include <algorithm>
 #include <cstddef>
 
@@ -28,7 +43,7 @@ __global__ __launch_bounds__(256) void ef_delta_kernel(const float* __restrict__
                                                        const float* __restrict__ residual, float* __restrict__ d, long n) {
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    d[i] = local[i] - global[i] + (residual ? residual[i] : 0.f);
+    d[i] = __fadd_rn(__fsub_rn(local[i], global[i]), residual ? residual[i] : 0.f);
 }
 
 // out[idx[i]] += scale * val[i] for ONE rank's payload.  Indices are unique within a
@@ -40,7 +55,7 @@ __global__ __launch_bounds__(256) void scatter_add_rank_kernel(float* __restrict
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
     const int j = idx[i];
-    if (j >= 0 && j < n) out[j] += scale * val[i];
+    if (j >= 0 && j < n) out[j] = __fmaf_rn(scale, val[i], out[j]);
   }
 }
 
@@ -55,24 +70,25 @@ __global__ __launch_bounds__(256) void quant_int8_kernel(const float* __restrict
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = a;
   __syncthreads();
   const float amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-  const float s = amax > 0.f ? amax / 127.f : 1.f;
+  const float t = __fdiv_rn(amax, 127.f);
+  const float s = t > 0.f ? t : 1.f;   // t == 0: a zero chunk, or a subnormal amax whose quotient underflowed
   if (i < n) {
-    const float r = rintf(v / s);
+    const float r = rintf(__fdiv_rn(v, s));
     const int qi = (int)fminf(fmaxf(r, -127.f), 127.f);
     q[i] = (signed char)qi;
-    if (residual) residual[i] = v - (float)qi * s;
+    if (residual) residual[i] = __fmaf_rn(-(float)qi, s, v);
   }
   if (threadIdx.x == 0) scales[blockIdx.x] = s;
 }
 
-// out[i] += scale * sum_r q[r][i] * scales[r][i/256]
+// out[i] += scale * sum_r q[r][i] * scales[r][i/256], ranks in order (roundings: the header comment)
 __global__ __launch_bounds__(256) void dequant_accum_kernel(const signed char* __restrict__ q, const float* __restrict__ scales,
                                                             int R, long n, long nchunks, float* __restrict__ out, float scale) {
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float acc = 0.f;
-    for (int r = 0; r < R; ++r) acc += (float)q[(long)r * n + i] * scales[(long)r * nchunks + (i >> 8)];
-    out[i] += scale * acc;
+    for (int r = 0; r < R; ++r) acc = __fmaf_rn((float)q[(long)r * n + i], scales[(long)r * nchunks + (i >> 8)], acc);
+    out[i] = __fmaf_rn(scale, acc, out[i]);
   }
 }
 

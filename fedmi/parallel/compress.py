@@ -7,15 +7,20 @@ channel) and compresses the *update* instead:
 
 * ``topk``  — each client sends the k largest-magnitude entries of
   d = (w_local - w_global) + e (error feedback e carries the rest to the next
-  round); selection is exact, on the GPU in 4 launches and 2 passes over the
-  state (csrc/kernels/compress.hip ``launch_topk_ef``: fused delta + 11-bit
-  histogram, bin pick, wave-aggregated compaction of the certain winners and the
-  boundary-bin candidates, exact candidate select); (idx, val) pairs are all-gathered (RCCL, or the
+  round); selection is exact, on the GPU in 3 launches (6 from 1 M entries) and
+  2 passes over the state (csrc/kernels/compress.hip ``launch_topk_ef``: fused
+  delta + 11-bit histogram, wave-aggregated compaction of the certain winners and
+  the boundary-bin candidates with the bin pick inside it, exact candidate
+  select); (idx, val) pairs are all-gathered (RCCL, or the
   hipIpc peer kernels of :mod:`fedmi.parallel.peer`) and applied to the global
   model in rank order without atomics, so every client holds a bit-identical
   global model.  Payload per client: 8k bytes.
 * ``int8``  — per-256-element absmax int8 quantisation with error feedback;
   payload n + 4n/256 bytes (~3.9x smaller than fp32).
+
+The CPU branches below are the kernels' twin: they follow the single-rounding
+formulas in the header of csrc/kernels/compress.hip and give the kernels' bits
+(tests/int8_check.py is the independent exact reference of both).
 
 After aggregation every client holds w_global' = w_global + mean(sparse d),
 exactly like dense FedAvg when k = n.
@@ -37,6 +42,22 @@ from .. import native
 
 def _world(group) -> int:
     return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+
+
+def _fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """fp32 ``fma(a, b, c)``: ONE rounding of a * b + c, like the kernels' ``__fmaf_rn`` (the roundings are listed
+    in the header of csrc/kernels/compress.hip).  The product of two fp32 (or int8) values is exact in fp64; the
+    fp64 sum is rounded to odd (TwoSum gives the sign of what the addition dropped), after which the final
+    rounding to fp32 is the same as rounding the exact sum (fp64 carries more than 2 extra bits)."""
+    p = a.double() * b.double()
+    c = c.double()
+    hi = p + c
+    t = hi - p
+    lo = (p - (hi - t)) + (c - t)                       # hi + lo == p + c exactly
+    even = (hi.view(torch.int64) & 1) == 0
+    side = torch.where(lo > 0, torch.full_like(hi, float("inf")), torch.full_like(hi, float("-inf")))
+    hi = torch.where((lo != 0) & even, torch.nextafter(hi, side), hi)
+    return hi.float()
 
 
 PROBE = None          # diagnostics hook (client agent, FEDMI_DEBUG_STATS=1): called with a phase tag
@@ -174,8 +195,10 @@ class TopKCompressor(_EFCompressor):
             self._nat.scatter_add_ranked(native.stream_handle(self.dev), self.global_ref.data_ptr(),
                                          idx_all.data_ptr(), val_all.data_ptr(), w, self.k, 1.0 / w, self.n)
         else:
-            for r in range(w):                 # rank order, like the GPU path
-                self.global_ref.index_add_(0, idx_all[r].long(), val_all[r] * (1.0 / w))
+            scale = torch.tensor(1.0 / w, dtype=torch.float32, device=self.dev)
+            for r in range(w):                 # rank order and one fma per entry, like the GPU path
+                j = idx_all[r].long()          # (unique within a rank)
+                self.global_ref[j] = _fma32(scale, val_all[r], self.global_ref[j])
         x.copy_(self.global_ref)
         _probe("scatter")
 
@@ -199,11 +222,12 @@ class Int8Compressor(_EFCompressor):
             pad[:self.n] = self.d
             blocks = pad.view(self.nchunks, self.CHUNK)
             amax = blocks.abs().amax(1)
-            s = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+            t = amax / torch.full_like(amax, 127.0)      # a true fp32 division (not a product with 1 / 127)
+            s = torch.where(t > 0, t, torch.ones_like(t))   # t == 0: a zero chunk, or amax / 127 underflowed
             q = torch.round(blocks / s[:, None]).clamp_(-127, 127)
             self.q.copy_(q.view(-1)[:self.n].to(torch.int8))
             self.scales.copy_(s)
-            self.residual.copy_(self.d - (q * s[:, None]).view(-1)[:self.n])
+            self.residual.copy_(_fma32(-q, s[:, None], blocks).view(-1)[:self.n])
 
     # the fused peer kernel (quantise + exchange + dequantise-average in one launch); False: the unfused
     # reference path (tests compare the two bit for bit)
@@ -231,8 +255,11 @@ class Int8Compressor(_EFCompressor):
                                     self.global_ref.data_ptr(), 1.0 / w)
         else:
             idx = torch.arange(self.n, device=self.dev) // self.CHUNK
-            deq = q_all.float() * s_all[:, idx]
-            self.global_ref.add_(deq.sum(0) / w)
+            acc = torch.zeros_like(self.global_ref)
+            for r in range(w):                 # rank order, one fma per rank and entry, like the kernels
+                acc = _fma32(q_all[r], s_all[r][idx], acc)
+            scale = torch.tensor(1.0 / w, dtype=torch.float32, device=self.dev)
+            self.global_ref.copy_(_fma32(scale, acc, self.global_ref))
         x.copy_(self.global_ref)
 
 

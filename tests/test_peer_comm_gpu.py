@@ -15,6 +15,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+import int8_check as ic
+
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(240)]
 
 SIZES = [5, 62006, 1 << 20 | 3]
@@ -115,8 +117,11 @@ def test_peer_twoshot_bit_exact(world):
 # (kind, n, blocks): consecutive calls with different grid sizes and payload sizes.  Every call
 # must advance the communicator-wide call counter on ALL 256 epoch words (so the staging-slot
 # parity is one call number), and every result must stay bit-exact.
-MIXED = [("f32", 1 << 20, 128), ("i64", 3, 1), ("f32", 4099, 1), ("gather", 1 << 16, 0), ("f32", 1 << 20, 7),
-         ("f32", 64, 3), ("i64", 5, 1), ("gather", 48, 0), ("f32", 1 << 20, 0), ("f32", 1000, 128)]
+# The int8 + error-feedback calls lay the slot out differently (q bytes, then fp32 scales from n16): they sit
+# between f32 and gather calls of other sizes, so a stale line of either would show against the exact reference.
+MIXED = [("f32", 1 << 20, 128), ("i8", 62006, 0), ("i64", 3, 1), ("f32", 4099, 1), ("gather", 1 << 16, 0),
+         ("i8", 257, 1), ("f32", 1 << 20, 7), ("f32", 64, 3), ("i64", 5, 1), ("gather", 48, 0),
+         ("i8", 1 << 18 | 3, 64), ("f32", 1 << 20, 0), ("f32", 1000, 128)]
 
 
 def _mixed_worker(rank, world, path, algo, q):
@@ -139,6 +144,17 @@ def _mixed_worker(rank, world, path, algo, q):
                 if not torch.equal(x.cpu(), _expected(world, it, n)):
                     res["ok"] = False
                     res["msgs"].append(f"f32 it={it} n={n} blocks={blocks}")
+            elif kind == "i8":
+                # the communicator's own entry point; round 0 of the reference's inputs on the first pass over
+                # MIXED, round 1 (carried residuals) on the second
+                xs, g0, rs, g1, rs1 = ic.run_rounds("randn", n, world, 2)[it // len(MIXED)]
+                x, g, r = (torch.from_numpy(a.copy()).to(dev) for a in (xs[rank], g0, rs[rank]))
+                pc.comm.allreduce_int8_ef(native.stream_handle(dev), x.data_ptr(), g.data_ptr(), r.data_ptr(), n,
+                                          1.0 / world, blocks)
+                for name, got, exp in (("x", x, g1), ("g", g, g1), ("r", r, rs1[rank])):
+                    if not torch.equal(got.cpu(), torch.from_numpy(exp)):
+                        res["ok"] = False
+                        res["msgs"].append(f"i8 it={it} n={n} blocks={blocks}: {name}")
             elif kind == "i64":
                 iv = torch.arange(n, dtype=torch.int64, device=dev) * (rank + 1) - 3 * it
                 pc.allreduce_mean_(iv)
@@ -272,7 +288,21 @@ class _Flat:
         return self.t
 
 
+# (case, n): every size with randn -- 4 * 256 * 256 + 259 is 1026 chunks, the fused kernel's block cap plus a second
+# stride with a ragged tail -- and every other data case at the odd-tailed LeNet size and at one chunk plus one entry
+I8_SIZES = [1, 255, 256, 257, 1027, 62006, 4 * 256 * 256 + 259]
+I8_COMBOS = [("randn", n) for n in I8_SIZES] + [(c, n) for c in ic.CASES if c != "randn" for n in (257, 62006)]
+
+
+def _first_diff(got: torch.Tensor, exp: torch.Tensor) -> str:
+    bad = (got != exp).nonzero().flatten()
+    i = int(bad[0])
+    return f"{bad.numel()} entries, first at {i} (chunk {i // 256}, lane {i % 256}): {got[i].item()!r} != {exp[i].item()!r}"
+
+
 def _int8_worker(rank, world, path, q):
+    import hashlib
+
     import torch.distributed as dist
 
     torch.cuda.set_device(0)
@@ -282,38 +312,53 @@ def _int8_worker(rank, world, path, q):
     store = dist.FileStore(path, world)
     dev = torch.device("cuda", 0)
     res = {"ok": True, "msgs": []}
-    n = 62006                                          # LeNet's flat state (odd tail chunk)
-    pc = PeerAllReduce(rank, world, 4 * n + 4096, store, tag="i8")
-    g0 = torch.randn(n, generator=torch.Generator().manual_seed(5)).to(dev)
-    outs = {}
-    for fused in (True, False):
-        x = (g0 + 0.01 * _data(rank, 3, n).to(dev)).contiguous()
-        comp = Int8Compressor(_Flat(x))
-        comp.global_ref.copy_(g0)
-        comp.residual.copy_(1e-3 * _data(rank, 4, n).to(dev))
-        comp.fused = fused
-        for _ in range(3):                              # error feedback carried over rounds
-            x.add_(0.01 * _data(rank, 7 + _, n).to(dev))
-            comp.aggregate(_Flat(x), transport=pc)
-        torch.cuda.synchronize()
-        outs[fused] = (x.cpu(), comp.global_ref.cpu(), comp.residual.cpu())
-    for a, b, name in zip(outs[True], outs[False], ("x", "g", "r")):
-        if not torch.equal(a, b):
-            res["ok"] = False
-            res["msgs"].append(f"{name} fused != unfused: max {(a - b).abs().max().item():.3e}")
-    import hashlib
+    digest = hashlib.sha256()
 
-    res["x"] = hashlib.sha256(outs[True][0].numpy().tobytes()).hexdigest()   # (no tensors through the queue)
-    res["err"] = pc.error()
-    pc.close()
+    def fail(msg):
+        res["ok"] = False
+        if len(res["msgs"]) < 20:
+            res["msgs"].append(msg)
+
+    try:
+        pc = PeerAllReduce(rank, world, 4 * max(I8_SIZES) + 4096, store, tag="i8")
+        for case, n in I8_COMBOS:
+            g0, r0, _ = ic.inputs(case, n, world)
+            ref = ic.run_rounds(case, n, world)               # every rank's inputs rebuilt here, like _expected
+            outs = {}
+            for fused in (True, False):
+                x = torch.from_numpy(g0.copy()).to(dev)
+                comp = Int8Compressor(_Flat(x))
+                comp.residual.copy_(torch.from_numpy(r0[rank]))
+                comp.fused = fused
+                for k, (xs, _, _, g1, rs1) in enumerate(ref):   # error feedback carried over the rounds
+                    x.copy_(torch.from_numpy(xs[rank]))         # x = g_k + this round's update (host fp32 sum)
+                    comp.aggregate(_Flat(x), transport=pc)
+                    torch.cuda.synchronize()
+                    for name, got, exp in (("x", x, g1), ("g", comp.global_ref, g1), ("r", comp.residual, rs1[rank])):
+                        got, exp = got.cpu(), torch.from_numpy(exp)
+                        if not torch.equal(got, exp):
+                            fail(f"{case} n={n} fused={fused} round {k}: {name} != reference: {_first_diff(got, exp)}")
+                outs[fused] = (x.cpu(), comp.global_ref.cpu(), comp.residual.cpu())
+            for a, b, name in zip(outs[True], outs[False], ("x", "g", "r")):
+                if not torch.equal(a, b):
+                    fail(f"{case} n={n}: {name} fused != unfused: {_first_diff(a, b)}")
+            digest.update(outs[True][0].numpy().tobytes())      # (no tensors through the queue)
+        res["err"] = pc.error()
+        pc.close()
+    except Exception as e:  # pragma: no cover - reported to the parent
+        fail(repr(e))
+        res["err"] = -1
+    res["x"] = digest.hexdigest()
     q.put((rank, res))
 
 
-@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("world", [2, 3, 4])
 def test_int8_ef_fused_matches_unfused_bit_exact(world):
     """the one-launch int8 + error-feedback peer collective equals the unfused path (delta,
     quantise, two all-gathers, dequantise-accumulate) bit for bit -- x, the new global model and the residual --
-    and every rank ends on the same model."""
+    and every rank ends on the same model.  Both also equal the exact reference (int8_check.int8_round of every
+    rank's rebuilt inputs) after each of three rounds, at every size in I8_COMBOS; world 3 has the scale 1/3, where
+    scale * acc is not exact and an fma differs from a multiply and an add."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     with tempfile.TemporaryDirectory() as td:
