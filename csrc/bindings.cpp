@@ -33,6 +33,8 @@ void launch_scaffold_finish(hipStream_t, const float*, float*, float*, long, lon
 void launch_scaffold_begin(hipStream_t, float*, const float*, const float*, float*, float*, long);
 int dp_partials(long);
 void launch_dp(hipStream_t, float*, const float*, long, double*, double*, double, float, uint64_t, uint64_t, int);
+int robust_partials(long);
+void launch_robust_reduce(hipStream_t, const float*, long, int, long, int, float*, long long*, long long*);
 void launch_ef_delta(hipStream_t, const float*, const float*, const float*, float*, long);
 size_t topk_state_bytes();
 size_t topk_overflow_offset();
@@ -201,6 +203,29 @@ static void fedmi_bind(py::module_& m) {
   }, py::arg("stream"), py::arg("x"), py::arg("anchor"), py::arg("n"), py::arg("k"), py::arg("partial"),
      py::arg("stats"), py::arg("clip"), py::arg("z"), py::arg("world"), py::arg("key"), py::arg("draw"),
      py::arg("stages") = 7);
+
+  // Byzantine-robust aggregation (csrc/kernels/robust.hip): out[i] = the coordinate-wise trimmed mean (b_eff entries
+  // cut on either side; the median at b_eff = (W - 1) / 2) of rows[0][i] .. rows[W-1][i], rows ld floats apart;
+  // stats[r], r < W = the number of coordinates at which rank r was cut.  partial: robust_partials(n) x 16 int64.
+  m.def("robust_partials", [](long n) {
+    if (n < 0) throw std::invalid_argument("robust_partials: need n >= 0");
+    return robust_partials(n);
+  });
+  m.def("robust_reduce", [](uintptr_t st, uintptr_t rows, long ld, int W, long n, int b_eff, uintptr_t out,
+                            uintptr_t partial, uintptr_t stats) {
+    if (W < 2 || W > 16) throw std::invalid_argument("robust_reduce: W must be in 2..16");
+    if (b_eff < 0 || b_eff > (W - 1) / 2) throw std::invalid_argument("robust_reduce: need 0 <= b_eff <= (W - 1) / 2");
+    if (n < 0) throw std::invalid_argument("robust_reduce: need n >= 0");
+    if (ld < n || ld % 4) throw std::invalid_argument("robust_reduce: the row stride ld must be >= n and a multiple of 4");
+    if (!rows || !out || !partial || !stats) throw std::invalid_argument("robust_reduce: null buffer");
+    if ((rows | out) % 16) throw std::invalid_argument("robust_reduce: rows and out must be 16-byte aligned");
+    if ((partial | stats) % 8) throw std::invalid_argument("robust_reduce: partial and stats must be 8-byte aligned");
+    if (n == 0) return;
+    launch_robust_reduce(S(st), P<const float>(rows), ld, W, n, b_eff, P<float>(out), P<long long>(partial),
+                         P<long long>(stats));
+    check_last("robust_reduce");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("b_eff"), py::arg("out"),
+     py::arg("partial"), py::arg("stats"));
 
   // client-side drift correction of the flat gradient, between the backward pass and the SGD tail (kind: 0
   // fedprox -- g, p, anchor, mu; 1 scaffold -- g, corr, acc); the other kind's buffers may be 0

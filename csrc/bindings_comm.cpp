@@ -15,6 +15,7 @@ void fedmi_bind_comm(py::module_& m) {
   m.attr("PEER_MAX_RANKS") = fedmi::kPeerMaxRanks;
   m.attr("PEER_ONESHOT") = (int)fedmi::kPeerOneShot;
   m.attr("PEER_TWOSHOT") = (int)fedmi::kPeerTwoShot;
+  m.attr("PEER_MAX_BLOCKS") = fedmi::kPeerMaxBlocks;
   py::class_<PeerComm>(m, "PeerComm")
       .def(py::init<int, int, long long>(), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"))
       .def("handle", [](const PeerComm& c) {
@@ -35,6 +36,13 @@ void fedmi_bind_comm(py::module_& m) {
                              blocks);
            }, py::arg("stream"), py::arg("src"), py::arg("dst"), py::arg("n"), py::arg("scale"), py::arg("algo") = 0,
            py::arg("blocks") = 0)
+      .def("allreduce_robust_f32", [](PeerComm& c, uintptr_t st, uintptr_t in, uintptr_t out, long long n, int b_eff,
+                                      uintptr_t cut_partials, uintptr_t stats, int blocks) {
+             c.allreduce_robust_f32(S(st), reinterpret_cast<const float*>(in), reinterpret_cast<float*>(out), n, b_eff,
+                                    reinterpret_cast<long long*>(cut_partials), reinterpret_cast<long long*>(stats),
+                                    blocks);
+           }, py::arg("stream"), py::arg("src"), py::arg("dst"), py::arg("n"), py::arg("b_eff"),
+           py::arg("cut_partials"), py::arg("stats"), py::arg("blocks") = 0)
       .def("allreduce_int8_ef", [](PeerComm& c, uintptr_t st, uintptr_t x, uintptr_t g, uintptr_t r, long long n,
                                    float scale, int blocks) {
              c.allreduce_int8_ef(S(st), reinterpret_cast<float*>(x), reinterpret_cast<float*>(g),

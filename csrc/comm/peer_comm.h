@@ -73,6 +73,11 @@ class PeerComm {
 
   // out = scale * sum_p in_p  (fp32; in == out allowed)
   void allreduce_f32(hipStream_t st, const float* in, float* out, long long n, float scale, int algo, int blocks);
+  // out = the coordinate-wise trimmed mean over the ranks' in (b_eff entries cut on either side; the median at
+  // b_eff = (world - 1) / 2), kernels/robust_fold.h; stats[r] (int64, r < world) = the number of coordinates at which
+  // rank r was cut.  cut_partials: kPeerMaxBlocks x 16 int64 of scratch.  Capacity rule of allreduce_f32.
+  void allreduce_robust_f32(hipStream_t st, const float* in, float* out, long long n, int b_eff,
+                            long long* cut_partials, long long* stats, int blocks);
   // -c Y int8 + error feedback in ONE launch: d = x - g + r quantised per 256-chunk (r <- quantisation error),
   // g += scale * sum_p deq(q_p), x = g  (bit-identical to ef_delta + quant_int8 + all-gathers + dequant_accum)
   void allreduce_int8_ef(hipStream_t st, float* x, float* g, float* r, long long n, float scale, int blocks);

@@ -27,6 +27,8 @@
 // every block of this one has retired.
 #include "peer_comm.h"
 
+#include "kernels/robust_fold.h"
+
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
@@ -34,6 +36,7 @@
 
 namespace fedmi {
 void check_hip(hipError_t e, const char* what);
+void launch_robust_finish(hipStream_t, const long long*, int, int, long long*);   // kernels/robust.hip
 }
 
 namespace {
@@ -139,6 +142,53 @@ __global__ __launch_bounds__(256) void peer_oneshot_f32_kernel(PeerArgs a, const
     reinterpret_cast<float4*>(out)[i] = s;
   }
   if (b == 0 && t < tail) out[n4 * 4 + t] = scale * gather_sum1(a, slot, n4 * 4 + t);
+  end_call(a, b, ep);
+}
+
+// Byzantine-robust all-reduce (fedmi/parallel/robust.py): peer_oneshot_f32_kernel with the rank-ordered sum replaced
+// by the coordinate-wise trimmed mean of kernels/robust_fold.h over the peers' float4 granules.  The fold orders by
+// (key, rank), so every rank computes the same bits.  Same staging slot, barrier and call counter as every other
+// collective of the communicator.  partial[block][r] = the block's count of coordinates at which rank r was cut
+// (a block whose barrier failed writes nothing: the communicator's error word is set, the round is void).
+template <int W>
+__global__ __launch_bounds__(256) void peer_robust_f32_kernel(PeerArgs a, const float* in, float* out, long long n,
+                                                              int trim, long long* partial) {
+  const int b = blockIdx.x, t = threadIdx.x;
+  const uint32_t ep = begin_call(a, b);
+  const int slot = ep & 1;
+  const long long n4 = n >> 2, stride = (long long)gridDim.x * 256;
+  const int tail = (int)(n & 3);
+  float* mine = reinterpret_cast<float*>(region(a, a.rank, slot, 0));
+  for (long long i = (long long)b * 256 + t; i < n4; i += stride)
+    reinterpret_cast<float4*>(mine)[i] = reinterpret_cast<const float4*>(in)[i];
+  if (b == 0 && t < tail) mine[n4 * 4 + t] = in[n4 * 4 + t];
+  if (!peer_barrier(a, 0, b, ep)) return;
+  fedmi::RobustCuts<W> cuts;
+  for (long long i = (long long)b * 256 + t; i < n4; i += stride) {
+    float4 v[W];
+#pragma unroll
+    for (int p = 0; p < W; ++p) v[p] = reinterpret_cast<const float4*>(region(a, p, slot, 0))[i];
+    float o[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float x[W];
+#pragma unroll
+      for (int p = 0; p < W; ++p) x[p] = reinterpret_cast<const float*>(&v[p])[c];
+      uint32_t cut;
+      o[c] = fedmi::robust_fold<W>(x, trim, cut);
+      cuts.add(cut);
+    }
+    reinterpret_cast<float4*>(out)[i] = make_float4(o[0], o[1], o[2], o[3]);
+  }
+  if (b == 0 && t < tail) {
+    float x[W];
+#pragma unroll
+    for (int p = 0; p < W; ++p) x[p] = reinterpret_cast<const float*>(region(a, p, slot, 0))[n4 * 4 + t];
+    uint32_t cut;
+    out[n4 * 4 + t] = fedmi::robust_fold<W>(x, trim, cut);
+    cuts.add(cut);
+  }
+  cuts.store(partial + (long long)b * fedmi::kRobustMaxRanks);
   end_call(a, b, ep);
 }
 
@@ -472,6 +522,27 @@ void PeerComm::allreduce_f32(hipStream_t st, const float* in, float* out, long l
   else
     hipLaunchKernelGGL(peer_oneshot_f32_kernel, dim3(blocks), dim3(256), 0, st, a_, in, out, n, scale);
   check_hip(hipGetLastError(), "peer allreduce_f32 launch");
+}
+
+void PeerComm::allreduce_robust_f32(hipStream_t st, const float* in, float* out, long long n, int b_eff,
+                                    long long* cut_partials, long long* stats, int blocks) {
+  need(connected_ && a_.world >= 2, "PeerComm::allreduce_robust_f32: needs a connected communicator of 2..16 ranks");
+  need(n >= 0 && n * 4 <= a_.cap, "PeerComm::allreduce_robust_f32: payload exceeds capacity");
+  need(b_eff >= 0 && b_eff <= (a_.world - 1) / 2, "PeerComm::allreduce_robust_f32: need 0 <= b_eff <= (world - 1) / 2");
+  need((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+       "PeerComm::allreduce_robust_f32: buffers must be 16-byte aligned");
+  need(cut_partials && stats && ((reinterpret_cast<uintptr_t>(cut_partials) | reinterpret_cast<uintptr_t>(stats)) & 7) == 0,
+       "PeerComm::allreduce_robust_f32: cut_partials and stats must be non-null and 8-byte aligned");
+  if (n == 0) return;
+  if (blocks <= 0) blocks = default_blocks(n * 4, kPeerOneShot, a_.world);
+  need(blocks <= kPeerMaxBlocks, "PeerComm: too many blocks");
+  robust_dispatch(a_.world, [&](auto w) {
+    hipLaunchKernelGGL(peer_robust_f32_kernel<decltype(w)::value>, dim3(blocks), dim3(256), 0, st, a_, in, out, n,
+                       b_eff, cut_partials);
+  });
+  check_hip(hipGetLastError(), "peer allreduce_robust_f32 launch");
+  launch_robust_finish(st, cut_partials, blocks, a_.world, stats);
+  check_hip(hipGetLastError(), "peer robust_finish launch");
 }
 
 void PeerComm::allreduce_int8_ef(hipStream_t st, float* x, float* g, float* r, long long n, float scale, int blocks) {

@@ -30,6 +30,7 @@ SOURCES = [
     CSRC / "kernels" / "server_opt.hip",
     CSRC / "kernels" / "client_opt.hip",
     CSRC / "kernels" / "dp.hip",
+    CSRC / "kernels" / "robust.hip",
     CSRC / "kernels" / "compress.hip",
     CSRC / "kernels" / "conv_igemm.hip",
     CSRC / "kernels" / "cnn_ops.hip",

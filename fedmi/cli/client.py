@@ -24,6 +24,7 @@ from ..parallel.compress import make_compressor
 from ..parallel.dp import add_dp_flags, check_dp_flags, make_dp
 from ..parallel.fedavg import FedAvg
 from ..parallel.group import GroupManager
+from ..parallel.robust import add_robust_flags, check_robust_flags, make_robust
 from ..parallel.server_opt import add_server_opt_flags, make_server_opt
 from ..utils.metrics import MetricsLog, log
 
@@ -66,6 +67,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_server_opt_flags(ap)
     add_client_opt_flags(ap)
     add_dp_flags(ap)
+    add_robust_flags(ap)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--root", default=".")
     ap.add_argument("--metrics", default=None)
@@ -92,6 +94,7 @@ def main(argv=None) -> int:
     if a.client_mu < 0:
         ap.error("--client-mu must be >= 0")
     check_dp_flags(a, ap.error)
+    check_robust_flags(a, ap.error)
     gzip = a.compressFlag == "Y"
     dev = pick_device(a.device)
     if dev.type == "cuda":
@@ -117,6 +120,7 @@ def main(argv=None) -> int:
     fedavg = FedAvg(compressor=make_compressor(comp_kind, a.topk_ratio, trainer, a.compress_warmup),
                     client_opt=client_opt,
                     dp=make_dp(a.dp_clip, trainer, a.dp_noise, a.dp_delta, a.dp_seed, who=a.address),
+                    robust=make_robust(a.robust, trainer, a.robust_trim),
                     server_opt=make_server_opt(a.server_opt, trainer, a.server_lr, a.server_beta1, a.server_beta2,
                                                a.server_tau))
     n = trainer.float_state().numel()

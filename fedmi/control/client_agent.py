@@ -350,6 +350,9 @@ class ClientAgent(P.TrainerServicer):
             dp = getattr(self.fedavg, "dp", None)
             if dp is not None:
                 rec.update(dp.round_stats())    # update norm, clip scale, epsilon so far: no sync of its own
+            robust = getattr(self.fedavg, "robust", None)
+            if robust is not None:
+                rec.update(robust.round_stats())    # who was cut, how often: no sync of its own either
             self.round = rnd
             self._check_compressor(rnd)
             t4 = Timer()

@@ -101,6 +101,7 @@ class FedAvg:
     server_opt: Optional[object] = None      # fedmi.parallel.server_opt.ServerOpt (None: plain FedAvg)
     client_opt: Optional[object] = None      # fedmi.parallel.client_opt.ClientOpt (None: plain local SGD)
     dp: Optional[object] = None              # fedmi.parallel.dp.DpGuard (None: the raw update is aggregated)
+    robust: Optional[object] = None          # fedmi.parallel.robust.RobustAgg (None: the plain mean)
 
     def world(self) -> int:
         if self.transport is not None:
@@ -123,8 +124,9 @@ class FedAvg:
         return base
 
     def opts(self) -> list:
-        """The attached :class:`fedmi.parallel.replicated.ReplicatedState`: server and client optimizer, DP guard."""
-        return [o for o in (self.server_opt, self.client_opt, self.dp) if o is not None]
+        """The attached :class:`fedmi.parallel.replicated.ReplicatedState`: server and client optimizer, DP guard,
+        robust rule."""
+        return [o for o in (self.server_opt, self.client_opt, self.dp, self.robust) if o is not None]
 
     def snapshot_opts(self) -> None:
         for o in self.opts():
@@ -157,6 +159,10 @@ class FedAvg:
         if self.world() > 1:
             if self.compressor is not None:
                 self.compressor.aggregate(trainer, self.group, transport=self.transport)
+            elif self.robust is not None:
+                # the coordinate-wise median / trimmed mean of the clients' (clipped) models instead of their mean;
+                # the server step below takes it as its end point
+                self.robust.aggregate(trainer, self)
             else:
                 self._mean(trainer.float_state())
             for b in trainer.int_state():

@@ -131,6 +131,24 @@ class PeerAllReduce:
         self.calls += 1
         return dst
 
+    def allreduce_robust_(self, t: torch.Tensor, b_eff: int, partials: torch.Tensor, stats: torch.Tensor,
+                          blocks: int = 0) -> torch.Tensor:
+        """In place: t <- the coordinate-wise trimmed mean over ranks with ``b_eff`` values cut on either side (the
+        median at ``(world - 1) // 2``; fedmi.parallel.robust), one launch, bit-identical on every rank.
+        ``stats[r]`` (int64, r < world) <- the number of coordinates at which rank r was cut; ``partials`` is int64
+        scratch of ``PEER_MAX_BLOCKS`` x 16."""
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError("peer robust all-reduce needs a contiguous, 16-byte aligned fp32 tensor")
+        if partials.dtype != torch.int64 or stats.dtype != torch.int64 or stats.numel() < 16 or \
+                partials.numel() < 16 * self.nat.PEER_MAX_BLOCKS:
+            raise ValueError("peer robust all-reduce needs int64 stats[16] and partials[PEER_MAX_BLOCKS, 16]")
+        if not self._gate():
+            return t
+        self.comm.allreduce_robust_f32(self._stream(), t.data_ptr(), t.data_ptr(), t.numel(), int(b_eff),
+                                       partials.data_ptr(), stats.data_ptr(), int(blocks))
+        self.calls += 1
+        return t
+
     def int8_ef_allreduce_(self, x: torch.Tensor, g: torch.Tensor, r: torch.Tensor) -> None:
         """-c Y fused into the collective (one launch): x - g + r is quantised to int8 per 256-entry chunk with the
         quantisation error kept in ``r``, every rank's int8 payload is dequantised and averaged in rank order into

@@ -26,6 +26,43 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 N_TRAIN, N_TEST, BATCH = 50000, 10000, 128
+ATTACKS = ("none", "signflip", "scale", "nan")
+
+
+def attack_state(kind: str, start: torch.Tensor, x: torch.Tensor, scale: float) -> torch.Tensor:
+    """What a simulated Byzantine client sends instead of its trained state ``x``, given the round's starting model:
+    ``signflip``: start - A (x - start); ``scale``: start + A (x - start); ``nan``: all NaN."""
+    if kind == "signflip":
+        return start - scale * (x - start)
+    if kind == "scale":
+        return start + scale * (x - start)
+    if kind == "nan":
+        return torch.full_like(x, float("nan"))
+    raise ValueError(f"attack must be one of {ATTACKS[1:]}, not {kind!r}")
+
+
+def robust_stack(robust, states, nat=None):
+    """The robust aggregate of the simulated clients' float states (a list of equal-length fp32 tensors) and the cut
+    counts: ``robust_reduce`` (csrc/kernels/robust.hip) on a GPU, its torch twin elsewhere."""
+    from fedmi import native
+    from fedmi.parallel.robust import robust_reduce_torch
+
+    W, n = len(states), states[0].numel()
+    b = robust.cfg.b_eff(W)
+    if not states[0].is_cuda:
+        return robust_reduce_torch(torch.stack(states), b)
+    nat = nat or native.require()
+    dev = states[0].device
+    ld = (n + 3) & ~3
+    rows = torch.zeros((W, ld), dtype=torch.float32, device=dev)
+    for r, x in enumerate(states):
+        rows[r, :n].copy_(x)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    partial = torch.zeros((max(1, nat.robust_partials(n)), 16), dtype=torch.int64, device=dev)
+    stats = torch.zeros(16, dtype=torch.int64, device=dev)
+    nat.robust_reduce(native.stream_handle(dev), rows.data_ptr(), ld, W, n, b, out.data_ptr(), partial.data_ptr(),
+                      stats.data_ptr())
+    return out, stats[:W]
 
 
 def _eval_batch_bn(tr) -> None:
@@ -56,6 +93,7 @@ def _run_seed(a, seed, data, dev, out) -> None:
     from fedmi.engine.data import contiguous_schedule, label_shard_indices, strided_schedule
     from fedmi.parallel.client_opt import make_client_opt
     from fedmi.parallel.dp import make_dp
+    from fedmi.parallel.robust import make_robust
     from fedmi.parallel.server_opt import make_server_opt
 
     cfg = TrainerConfig(seed=seed, lr=a.lr, augment=not a.no_augment, use_graph=not a.no_graph)
@@ -87,9 +125,11 @@ def _run_seed(a, seed, data, dev, out) -> None:
     # one DP guard per simulated client: its own key, anchor and draw counter; each adds its 1/sqrt(W) noise share
     dps = [make_dp(a.dp_clip, tr, a.dp_noise, a.dp_delta, a.dp_seed, who=f"seed{seed}/client{r}")
            for r, tr in enumerate(clients)]
+    robust = make_robust(a.robust, clients[0], a.robust_trim)
     for rnd in range(1, a.rounds + 1):
         t0 = time.perf_counter()
         tstats = []
+        start = clients[0].float_state().clone() if a.attack != "none" else None   # every client holds it
         for tr in clients:
             tr.train_epoch()
             tstats.append(tr.train_stats())
@@ -103,7 +143,13 @@ def _run_seed(a, seed, data, dev, out) -> None:
             for tr, dp in zip(clients, dps):
                 if dp is not None:
                     dp.privatize(tr, W)
-            mean = torch.stack([tr.float_state() for tr in clients]).mean(0)
+            for tr in clients[W - a.attackers:] if a.attack != "none" else ():
+                tr.float_state().copy_(attack_state(a.attack, start, tr.float_state(), a.attack_scale))
+            cut = None
+            if robust is not None and W > 1:
+                mean, cut = robust_stack(robust, [tr.float_state() for tr in clients])
+            else:
+                mean = torch.stack([tr.float_state() for tr in clients]).mean(0)
             ints = [torch.div(sum(bs), W, rounding_mode="floor")
                     for bs in zip(*[[b.clone() for b in tr.int_state()] for tr in clients])]
             if server is not None:
@@ -143,6 +189,11 @@ def _run_seed(a, seed, data, dev, out) -> None:
             rec.update(dp_clip=a.dp_clip, dp_noise=a.dp_noise, dp_delta=a.dp_delta, dp_epsilon=rows[0]["dp_epsilon"],
                        dp_norm=[round(r.get("dp_norm", -1.0), 4) for r in rows],
                        dp_scale=[round(r.get("dp_scale", -1.0), 4) for r in rows])
+        if robust is not None:
+            rec.update(robust_kind=a.robust, robust_trim=robust.cfg.b_eff(W),
+                       robust_cut=cut.tolist() if cut is not None else None)
+        if a.attack != "none":
+            rec.update(attack=a.attack, attackers=a.attackers, attack_scale=a.attack_scale)
         line = json.dumps(rec)
         print(line, flush=True)
         if out:
@@ -182,10 +233,22 @@ def main(argv=None) -> int:
     from fedmi.parallel.dp import add_dp_flags, check_dp_flags
 
     add_dp_flags(ap)
+    from fedmi.parallel.robust import add_robust_flags, check_robust_flags
+
+    add_robust_flags(ap)
+    ap.add_argument("--attack", default="none", choices=list(ATTACKS),
+                    help="simulated Byzantine clients (the simulator only): the last --attackers clients send "
+                         "start - A (x - start) (signflip), start + A (x - start) (scale) or all NaN (nan) instead of "
+                         "their trained state x")
+    ap.add_argument("--attackers", type=int, default=1, metavar="K")
+    ap.add_argument("--attack-scale", type=float, default=10.0, metavar="A")
     a = ap.parse_args(argv)
     if a.client_mu < 0:
         ap.error("--client-mu must be >= 0")
     check_dp_flags(a, ap.error)
+    check_robust_flags(a, ap.error)
+    if a.attack != "none" and not 1 <= a.attackers <= a.clients:
+        ap.error("--attackers must lie in 1..--clients")
     if a.bn_eval == "batch" and a.engine == "native":
         ap.error("--bn-eval batch needs a PyTorch engine (fp32 / bf16)")
     if a.engine in ("fp32", "bf16"):
