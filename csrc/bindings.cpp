@@ -26,6 +26,7 @@ bool stamps_enabled();
 void read_stamps(unsigned long long*, bool);
 void set_ks1_diag(int);
 void launch_lenet_pack(hipStream_t, const float*, bf16*);
+void launch_lenet_prep_batch(hipStream_t, const uint8_t*, int, int, uint32_t, const int*, int, bf16*);
 void launch_sgd_flat(hipStream_t, float*, const float*, float*, long, float, float, float, float, int, int);
 void launch_server_opt(hipStream_t, float*, float*, float*, float*, long, long, int, float, float, float, float);
 void launch_drift_grad(hipStream_t, int, float*, const float*, const float*, const float*, float*, float, long);
@@ -78,6 +79,7 @@ static LeNetBuffers buffers_from(const py::dict& d) {
   b.train_stats = P<lenet::Stats>(get("train_stats"));
   b.eval_stats = P<lenet::Stats>(get("eval_stats"));
   b.round_ctr = P<int>(get("round_ctr"));
+  b.xprep = P<bf16>(get("xprep"));
   return b;
 }
 
@@ -106,6 +108,9 @@ static void fedmi_bind(py::module_& m) {
     d["CS"] = CS; d["FS"] = FS; d["F1W_N"] = F1W_N; d["DZ1_LD"] = DZ1_LD; d["PK_TOTAL"] = PK_TOTAL; d["F0"] = F0; d["F0P"] = F0P; d["NP1"] = NP1;
     d["MAX_TRAIN_BATCH"] = MAX_TRAIN_BATCH; d["FC_SPW"] = FC_SPW;
     d["IMG_BYTES"] = IMG_BYTES; d["STATS_BYTES"] = (int)sizeof(Stats);
+    d["PK_W1C"] = PK_W1C; d["PK_W2C"] = PK_W2C; d["PK_W2DG"] = PK_W2DG; d["PK_FC1"] = PK_FC1;
+    d["PK_FC2"] = PK_FC2; d["PK_FC2T"] = PK_FC2T; d["PK_FC3"] = PK_FC3;
+    d["XP_H"] = XP_H; d["XP_W"] = XP_W; d["XP_C"] = XP_C; d["XP_ELEMS"] = XP_ELEMS;
     return d;
   });
 
@@ -149,6 +154,12 @@ static void fedmi_bind(py::module_& m) {
                           P<const int>(round_ctr), augment, P<bf16>(act2), P<bf16>(act2T), tstride, P<bf16>(pool1),
                           P<uint8_t>(am1), P<uint8_t>(am2), P<lenet::Stats>(zero_stats));
     check_last("lenet_conv_fwd");
+  });
+  m.def("lenet_prep_batch", [](uintptr_t st, uintptr_t images, int base, int nb, uint32_t seed, uintptr_t round_ctr,
+                               int augment, uintptr_t xprep) {
+    launch_lenet_prep_batch(S(st), P<const uint8_t>(images), base, nb, seed, P<const int>(round_ctr), augment,
+                            P<bf16>(xprep));
+    check_last("lenet_prep_batch");
   });
   m.def("lenet_pack", [](uintptr_t st, uintptr_t params, uintptr_t pk) {
     launch_lenet_pack(S(st), P<const float>(params), P<bf16>(pk));

@@ -3,8 +3,8 @@
 // One local SGD step of the reference (src/main.py:146-151: zero_grad, forward, CE loss,
 // backward, SGD(m=0.9, wd=5e-4)) is TWO launches:
 //
-//   KS1 lenet_sample_step  one 16-wave workgroup per sample runs the sample's whole chain:
-//                          on-device RandomCrop(32,pad4)+HFlip+Normalize (src/main.py:37-42)
+//   KS1 lenet_sample_step  one 16-wave workgroup per sample runs the sample's whole chain: its prepared
+//                          image (below) straight into LDS
 //                          -> conv1 (MFMA) +bias+ReLU -> maxpool2 -> conv2 (MFMA) +bias+ReLU
 //                          -> maxpool2 -> fc1/fc2/fc3 -> CE -> FC backward -> conv backward
 //                          (maxpool/ReLU backward by argmax, conv2 wgrad + dgrad, conv1
@@ -12,7 +12,15 @@
 //                          fragment is one aligned 16-B read) -> the sample's gradient slab.
 //   KS2 lenet_sgd2         fc1/fc2/fc3 weight gradients as MFMA GEMMs over the batch, SGD
 //                          applied to each tile in the workgroup that computed it, the conv
-//                          slab combine, bias sums, loss/accuracy: fixed order, no atomics.
+//                          slab combine, bias sums, loss/accuracy: fixed order, no atomics.  The FC
+//                          tiles store their packed bf16 images from the tile's own (n, f).
+//                          Extra workgroups behind the SGD blocks prepare the NEXT step's images.
+//
+// Prepared images (prep_sample): on-device RandomCrop(32,pad4)+HFlip+Normalize (src/main.py:37-42) of
+// a batch, as bf16 channels-last [36][40][4] with pad and channel 3 zero -- KS1's LDS image, byte for
+// byte.  It depends on (seed, round counter, sample index) only, not on the parameters, so it is off
+// the KS2 -> KS1 chain: the KS2 launch of step i writes batch i + 1's images on the CUs KS1 has left
+// idle; lenet_prep_batch does it for an epoch's first step and for the eager step.
 //
 // Evaluation: lenet_conv_fwd (one 8-wave workgroup per sample, the same conv stack as KS1)
 // then lenet_fc_eval (16 samples per workgroup, fc1/fc2/fc3 as MFMA tiles, CE) and
@@ -30,7 +38,7 @@ using namespace lenet;
 #ifdef FEDMI_STAMPS
 __device__ unsigned long long fedmi_stamps[FEDMI_STAMP_KERNELS][FEDMI_STAMP_WGS][FEDMI_STAMP_SLOTS];
 // diagnostic build only: KS1 staging experiments (bit 0: skip the packed-weight loads, bit 1: every
-// workgroup reads sample 0's image).  Timing probes -- the numerics of such a step are meaningless.
+// workgroup reads prepared image 0).  Timing probes -- the numerics of such a step are meaningless.
 __device__ int fedmi_ks1_diag;
 #endif
 
@@ -72,7 +80,11 @@ FEDMI_DEV Aug aug_params(int augment, uint32_t seed, const int* round_ctr, int g
 
 // Normalised pixel of the augmented image (RandomCrop pads with pixel 0 BEFORE
 // ToTensor/Normalize, so out-of-image pixels become (0 - mean) / std).
+// Three separately rounded operations (multiply, subtract, multiply), by pragma: that is what the training
+// and eval kernels have always computed, and it is part of the step's bit-exact result.  Left to contraction,
+// a caller that inlines the in-image case on its own fuses pixel / 255 - mean into one FMA.
 FEDMI_DEV float aug_pixel(const uint8_t* raw, const Aug& a, int c, int y, int x) {
+#pragma clang fp contract(off)
   const int sy = y + a.i0 - 4;
   const int sx = (a.flip ? 31 - x : x) + a.j0 - 4;
   float v = 0.f;
@@ -83,6 +95,38 @@ FEDMI_DEV float aug_pixel(const uint8_t* raw, const Aug& a, int c, int y, int x)
 FEDMI_DEV void load_raw(const uint8_t* __restrict__ img, uint8_t* raw) {
   if ((int)threadIdx.x < IMG_BYTES / 16)
     reinterpret_cast<uint4*>(raw)[threadIdx.x] = reinterpret_cast<const uint4*>(img)[threadIdx.x];
+}
+
+// One part of a sample's prepared image (lenet_layout.h, XP_*): uint8 CHW -> crop / flip / normalise -> bf16
+// channels-last, pad and channel 3 written as zeros, one 16-B chunk (2 pixels) per thread.  A sample is
+// PREP_SPLIT 256-thread workgroups; each stages the whole 3 KB image (one load per thread, in flight together
+// with the round counter's) and converts its own third.  The pixels are aug_pixel's: KS1 used to compute the
+// same values in its own LDS.  raw: IMG_BYTES of LDS.
+constexpr int PREP_NT = 256;
+constexpr int XP_CHUNKS = XP_ELEMS / 8;                              // 720 16-B chunks per sample
+constexpr int PREP_SPLIT = (XP_CHUNKS + PREP_NT - 1) / PREP_NT;      // 3
+FEDMI_DEV void prep_sample(const uint8_t* __restrict__ images, int gidx, int part, uint32_t seed,
+                           const int* __restrict__ round_ctr, int augment, bf16* __restrict__ xp, uint8_t* raw) {
+  const int tid = threadIdx.x;
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (tid < IMG_BYTES / 16) v = reinterpret_cast<const uint4*>(images + (size_t)gidx * IMG_BYTES)[tid];
+  const Aug a = aug_params(augment, seed, round_ctr, gidx);
+  if (tid < IMG_BYTES / 16) reinterpret_cast<uint4*>(raw)[tid] = v;
+  __syncthreads();
+  const int e = part * PREP_NT + tid;
+  if (e < XP_CHUNKS) {
+    const int y = e / (XP_W / 2), x = (e - y * (XP_W / 2)) * 2;
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (bf16)0.f;
+    if (y < IMG && x < IMG) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) o[j * XP_C + c] = (bf16)aug_pixel(raw, a, c, y, x + j);
+    }
+    *reinterpret_cast<bf16x8*>(xp + e * 8) = o;
+  }
 }
 
 // NT = the launch's block size as a constant: blockDim.x is read from the dispatch packet, and the
@@ -419,7 +463,6 @@ constexpr int BW_O_XSH = 0, BW_O_P1SH = BW_O_XSH + BW_XSH * 2, BW_O_DY2W = BW_O_
 
 // LDS operands of one sample's conv backward (KS1 still holds them from its own forward).
 struct BwdLds {
-  const uint8_t* raw;     // uint8 CHW image
   const bf16* p1r;        // pool1 output, CHW [NP1]
   const uint8_t* am1s;    // pool1 argmax codes [NP1]
   const uint8_t* am2s;    // pool2 argmax codes [F0]
@@ -428,10 +471,10 @@ struct BwdLds {
   bf16* xsh; bf16* p1sh; bf16* dY2w; bf16* dY2c; bf16* dY1; float* db; float* w1part;
 };
 
-FEDMI_DEV BwdLds bwd_lds(unsigned char* scratch, const uint8_t* raw, const bf16* p1r, const uint8_t* am1s,
+FEDMI_DEV BwdLds bwd_lds(unsigned char* scratch, const bf16* p1r, const uint8_t* am1s,
                          const uint8_t* am2s, const float* dxs, const bf16* wdg) {
   BwdLds L;
-  L.raw = raw; L.p1r = p1r; L.am1s = am1s; L.am2s = am2s; L.dxs = dxs; L.wdg = wdg;
+  L.p1r = p1r; L.am1s = am1s; L.am2s = am2s; L.dxs = dxs; L.wdg = wdg;
   L.xsh = reinterpret_cast<bf16*>(scratch + BW_O_XSH);
   L.p1sh = reinterpret_cast<bf16*>(scratch + BW_O_P1SH);
   L.dY2w = reinterpret_cast<bf16*>(scratch + BW_O_DY2W);
@@ -679,10 +722,11 @@ FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int s
 // KS1 + KS2: the per-sample training step (the default training path).
 //
 // KS1 lenet_sample_step: ONE 16-wave workgroup per sample runs the WHOLE chain that
-// has no cross-sample dependency: augment -> conv stack forward -> fc1/fc2/fc3 ->
-// cross-entropy -> FC backward down to d(pool2) -> conv stack backward -> the
-// sample's conv gradient slab.  Every forward operand the backward needs (image,
-// pool1, argmax codes, act2) stays in LDS: no flag hand-off between workgroups
+// has no cross-sample dependency: its prepared image (augmented a step ahead by
+// prep_sample: the previous KS2's extra workgroups or lenet_prep_batch) loaded into
+// LDS -> conv stack forward -> fc1/fc2/fc3 -> cross-entropy -> FC backward down to
+// d(pool2) -> conv stack backward -> the sample's conv gradient slab.  Every forward
+// operand the backward needs (image, pool1, argmax codes, act2) stays in LDS: no flag hand-off between workgroups
 // (nothing waits on another workgroup, so a shared GPU can never deadlock it), no
 // restaging from global memory, one kernel boundary less than K12 -> K3.  The FC
 // layers of ONE sample are GEMVs: VALU dot products over 16-B weight chunks of the
@@ -711,7 +755,7 @@ static_assert(AUX_BYTES <= MAX_TRAIN_BATCH * F0 * 4, "FC side buffers must fit i
 // whose idle time up to dX also hosts the forward's two images (x and pool1, channels-last).  Nothing of the
 // forward aliases the backward's scratch, so that is cleared while the stage loads are in flight and the
 // shifted copies are built during the conv2 phase (the image's by the waves conv2 leaves idle).
-constexpr int S_O_RAW = 0, S_O_P1R = 3072, S_O_AM1 = S_O_P1R + 2368, S_O_AM2 = S_O_AM1 + 1184,
+constexpr int S_O_P1R = 0, S_O_AM1 = S_O_P1R + 2368, S_O_AM2 = S_O_AM1 + 1184,
               S_O_X = S_O_AM2 + 416, S_O_DX = S_O_X + F0P * 2, S_O_WDG = S_O_DX + F0 * 4,
               S_O_FC = S_O_WDG + 16 * BW_WDGS * 2, S_O_W1C = S_O_FC + 2048, S_O_W2C = S_O_W1C + 16 * 136 * 2,
               S_O_SCR = S_O_W2C + 16 * 232 * 2;
@@ -763,9 +807,9 @@ FEDMI_DEV float row_sum16(float v) {
 }
 
 __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
-    const uint8_t* __restrict__ images, int sample_base, int nb,
+    const bf16* __restrict__ xprep,      // [nb][XP_ELEMS] this batch's prepared images (prep_sample)
+    int nb,
     const bf16* __restrict__ pk, const float* __restrict__ params,
-    uint32_t seed, const int* __restrict__ round_ctr, int augment,
     const int* __restrict__ labels,      // labels of this batch (already offset)
     bf16* __restrict__ act2T,            // [F0P][128]
     bf16* __restrict__ h1T,              // [128][128]
@@ -777,10 +821,8 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
   const int s = blockIdx.x;
   if (s >= nb) return;
   [[maybe_unused]] const int stamp_wg = s;
-  const int gidx = sample_base + s;
   const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
   const int kq = (lane >> 4) * 8, n16 = lane & 15, rq = (lane >> 4) * 4;
-  uint8_t* raw = smem + S_O_RAW;
   bf16* p1r = reinterpret_cast<bf16*>(smem + S_O_P1R);
   uint8_t* am1s = smem + S_O_AM1;
   uint8_t* am2s = smem + S_O_AM2;
@@ -791,52 +833,56 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
   float* red = reinterpret_cast<float*>(smem + S_O_RED);
   bf16* xcl = reinterpret_cast<bf16*>(smem + S_O_RED + S_R_XCL);
   bf16* p1cl = reinterpret_cast<bf16*>(smem + S_O_RED + S_R_P1);
-  const BwdLds L = bwd_lds(smem + S_O_SCR, raw, p1r, am1s, am2s, dxs, wdg);
+  const BwdLds L = bwd_lds(smem + S_O_SCR, p1r, am1s, am2s, dxs, wdg);
   FEDMI_STAMP(0, 0);
 
-  // ---- stage: image (192 x 16 B) and the conv2 dgrad weight image (832 x 16 B) -- one
-  //      16-B load per thread; both land while the x image is zeroed and the augmentation drawn
+  // ---- stage: the prepared image (720 x 16 B, pad and channel 3 already zero: it lands in xcl as it is) and
+  //      the packed weight images, next to the clear of the backward's scratch
   bf16* w1c = reinterpret_cast<bf16*>(smem + S_O_W1C);
   bf16* w2c = reinterpret_cast<bf16*>(smem + S_O_W2C);
   bf16* w3s = reinterpret_cast<bf16*>(smem + S_O_W3);
   float bias1, bias2;
-  Aug a;
   {
-    // 192 image + 832 dgrad-weight + 256 conv1-weight + 448 conv2-weight + 192 fc3 16-B chunks (<= 2 per thread)
-    constexpr int NI = IMG_BYTES / 16, NWD = 16 * KDGP / 8, NW1 = 16 * K1C / 8, NW2 = 16 * K2C / 8, NW3 = 16 * 96 / 8;
-    constexpr int E1 = NI, E2 = E1 + NWD, E3 = E2 + NW1, E4 = E3 + NW2, E5 = E4 + NW3;
-    static_assert(E5 <= 2 * NT_CONV, "stage: two chunks per thread");
-    uint4 v[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+    // 720 image + 832 dgrad-weight + 256 conv1-weight + 448 conv2-weight + 192 fc3 16-B chunks (<= 3 per thread)
+    constexpr int NWD = 16 * KDGP / 8, NW1 = 16 * K1C / 8, NW2 = 16 * K2C / 8, NW3 = 16 * 96 / 8;
+    constexpr int NCH = 3;
+    constexpr int E1 = XP_CHUNKS, E2 = E1 + NWD, E3 = E2 + NW1, E4 = E3 + NW2, E5 = E4 + NW3;
+    static_assert(E5 <= NCH * NT_CONV, "stage: three chunks per thread");
+    static_assert(XP_ELEMS == 36 * 40 * 4 && (S_O_RED + S_R_XCL) % 16 == 0, "the prepared image is xcl, 16-B chunks");
+    uint4 v[NCH];
 #ifdef FEDMI_STAMPS
     const int dg = fedmi_ks1_diag;
-    const size_t img_sample = (dg & 2) ? 0 : (size_t)gidx;
+    const size_t img_sample = (dg & 2) ? 0 : (size_t)s;
     const int lim = (dg & 1) ? E1 : E5;
 #else
-    const size_t img_sample = (size_t)gidx;
+    const size_t img_sample = (size_t)s;
     constexpr int lim = E5;
 #endif
+    // every load unconditional from a selected address: the segments do not end on wave boundaries, and with
+    // one divergent branch per segment the stage took 5.6k cycles against 4.3k this way (the compiler split
+    // each 16-B load into four).  Chunks past E5 re-read a line of the image that is in use anyway and are not
+    // stored.  The kernel sits at the 128-VGPR cap: check for spills after any change here.
+    static_assert(PK_W2DG % 8 == 0 && PK_W1C % 8 == 0 && PK_W2C % 8 == 0 && PK_FC3 % 8 == 0, "16-B chunks");
+    const uint4* xp4 = reinterpret_cast<const uint4*>(xprep + img_sample * XP_ELEMS);
+    const uint4* pk4 = reinterpret_cast<const uint4*>(pk);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < NCH; ++u) {
       const int e = tid + u * NT_CONV;
-      if (e < E1) v[u] = reinterpret_cast<const uint4*>(images + img_sample * IMG_BYTES)[e];
-      else if (e >= lim) {}
-      else if (e < E2) v[u] = reinterpret_cast<const uint4*>(pk + PK_W2DG)[e - E1];
-      else if (e < E3) v[u] = reinterpret_cast<const uint4*>(pk + PK_W1C)[e - E2];
-      else if (e < E4) v[u] = reinterpret_cast<const uint4*>(pk + PK_W2C)[e - E3];
-      else if (e < E5) v[u] = reinterpret_cast<const uint4*>(pk + PK_FC3)[e - E4];
+      const int wo = e < E2 ? PK_W2DG / 8 + (e - E1) : e < E3 ? PK_W1C / 8 + (e - E2)
+                   : e < E4 ? PK_W2C / 8 + (e - E3) : PK_FC3 / 8 + (e - E4);
+      const uint4* src = (e >= E1 && e < lim) ? pk4 + wo : xp4 + min(e, E1 - 1);
+      v[u] = *src;
     }
     // the other global reads of the kernel's start go out in the same wave of requests (one
     // memory latency for the whole stage instead of one per dependent group)
     bias1 = n16 < C1 ? params[P_C1B + n16] : 0.f;
     bias2 = params[P_C2B + n16];
-    a = aug_params(augment, seed, round_ctr, gidx);
-    zero_lds<NT_CONV>(xcl, 36 * 40 * 4 * 2);
     bwd_zero(L);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < NCH; ++u) {
       const int e = tid + u * NT_CONV;
       if (e < E1) {
-        reinterpret_cast<uint4*>(raw)[e] = v[u];
+        reinterpret_cast<uint4*>(xcl)[e] = v[u];
       } else if (e < E2) {
         const int w = e - E1, row = w / (KDGP / 8), col = w - row * (KDGP / 8);
         reinterpret_cast<uint4*>(wdg + row * BW_WDGS)[col] = v[u];
@@ -857,17 +903,12 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
     const int g = ks * 4 + (lane >> 4);
     go1[ks] = g < 15 ? ((g / 3) * 40 + 2 * (g % 3)) * 4 : 0;
   }
-  __syncthreads();
+  __syncthreads();             // image and weights in LDS: conv1 starts here
   FEDMI_STAMP(1, 7);
+  FEDMI_STAMP(0, 1);
   bf16x8 wb1[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) wb1[ks] = ld8(w1c + n16 * S_W1C_LD + ks * 32 + kq);
-  for (int e = tid; e < IMG_BYTES; e += NT_CONV) {
-    const int c = e >> 10, y = (e >> 5) & 31, x = e & 31;
-    xcl[(y * 40 + x) * 4 + c] = (bf16)aug_pixel(raw, a, c, y, x);
-  }
-  __syncthreads();
-  FEDMI_STAMP(0, 1);
 
   // ---- conv1 (+bias+ReLU) with maxpool #1 in registers: a tile's 16 rows are 4 pooling windows x their 4
   //      positions in argmax-code order (row 4g + r, r = dy * 2 + dx: 0=(0,0) 1=(0,1) 2=(1,0) 3=(1,1)), so the
@@ -963,7 +1004,7 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
     bwd_build_shifted_p1(L, tid, 7 * 64);   // the shorter of the two builders rides behind conv2
   } else {
     // waves 7..15: the act2 row padding 400..415, then the conv backward's column-shifted copies of the
-    // image (final since the augmentation's barrier; pool1's copies: waves 0..6 above)
+    // image (final since the stage's barrier; pool1's copies: waves 0..6 above)
     if (tid < 7 * 64 + (F0P - F0)) {
       const int e = F0 + tid - 7 * 64;
       xrow[e] = (bf16)0.f;
@@ -1169,14 +1210,28 @@ __global__ __launch_bounds__(256) void lenet_pack(const float* __restrict__ para
 // ---------------------------------------------------------------------------
 constexpr int SGD_NA = (CS + 15) / 16;           // 180
 
-FEDMI_DEV void sgd_apply(int i, float grad, float p, float m, float* __restrict__ params, float* __restrict__ mom,
-                         bf16* __restrict__ pk, float lr, float momentum, float wd) {
-  const float d = grad + wd * p;
-  const float b = momentum * m + d;
-  const float np = p - lr * b;
+// Returns the new parameter: the caller stores its bf16 copy into the packed image(s), if it has any.
+// The three lines are FMAs by name: that is what the compiler's contraction made of `grad + wd * p`,
+// `momentum * m + d` and `p - lr * b` at every call site, and it is part of the step's bit-exact result.
+// Left to contraction, a call site whose neighbours change can turn into a packed multiply (wd * p and
+// momentum * m in one v_pk_mul_f32) with separately rounded adds.
+FEDMI_DEV float sgd_update(int i, float grad, float p, float m, float* __restrict__ params, float* __restrict__ mom,
+                           float lr, float momentum, float wd) {
+  const float d = __builtin_fmaf(wd, p, grad);
+  const float b = __builtin_fmaf(momentum, m, d);
+  const float np = __builtin_fmaf(-lr, b, p);
   mom[i] = b;
   params[i] = np;
-  pack_one(i, np, pk);
+  return np;
+}
+
+// Parameter i by its flat index alone: the conv slab blocks, one of which straddles the conv1.weight /
+// conv1.bias / conv2.weight borders.  The FC tiles know their (n, f) and address the pack stores from
+// them (pack_one's range chain and constant divisions, inlined per element, were 2.4k cycles of an
+// fc1 tile wave); biases have no packed image.
+FEDMI_DEV void sgd_apply(int i, float grad, float p, float m, float* __restrict__ params, float* __restrict__ mom,
+                         bf16* __restrict__ pk, float lr, float momentum, float wd) {
+  pack_one(i, sgd_update(i, grad, p, m, params, mom, lr, momentum, wd), pk);
 }
 
 // Masks the sample columns >= nb of an operand fragment (8 consecutive samples from s0).
@@ -1233,13 +1288,25 @@ __global__ __launch_bounds__(256) void lenet_sgd2(
     const float* __restrict__ conv_slab, int nb,
     const bf16* __restrict__ act2T, const bf16* __restrict__ h1T, const unsigned char* __restrict__ aux,
     const bf16* __restrict__ dZ1T, float lr, float momentum, float wd,
-    int* __restrict__ round_ctr, Stats* __restrict__ stats)
+    int* __restrict__ round_ctr, Stats* __restrict__ stats,
+    // blocks >= SGD2_GRID: the NEXT step's prepared images (next_nb == 0: none), on the CUs KS1 has just left.
+    // They read the round counter through aug_ctr; the launch that bumps it (an epoch's last) carries none.
+    const uint8_t* __restrict__ images, int next_base, int next_nb, uint32_t seed,
+    const int* __restrict__ aug_ctr, int augment, bf16* __restrict__ xprep)
 {
   __shared__ float red[16][17];
+  __shared__ __attribute__((aligned(16))) uint8_t raw[IMG_BYTES];
   const int b = blockIdx.x, tid = threadIdx.x, wave = wave_id(), lane = lane_id();
   const int n16 = lane & 15, rq = (lane >> 4) * 4;
   [[maybe_unused]] const int stamp_wg = b;
   FEDMI_STAMP(3, 0);
+  if (b >= SGD2_GRID) {
+    const int pb = b - SGD2_GRID, sp = pb / PREP_SPLIT;
+    if (sp < next_nb)
+      prep_sample(images, next_base + sp, pb - sp * PREP_SPLIT, seed, aug_ctr, augment, xprep + (size_t)sp * XP_ELEMS, raw);
+    FEDMI_STAMP(3, 1);
+    return;
+  }
   if (b < SGD_NA) {                                   // conv params: K4's slab combine
     const int pl = tid & 15, g = tid >> 4;
     const int i = b * 16 + pl;
@@ -1276,9 +1343,11 @@ __global__ __launch_bounds__(256) void lenet_sgd2(
       const f32x4 acc = batch_tile(dZ1T + (size_t)nt * 16 * DZ1_LD, act2T + (size_t)ft * 16 * MAX_TRAIN_BATCH, nb,
                                    params, mom, idx, p, m);
       FEDMI_STAMP(3, 2);    // operands landed + MFMA (wave 0's tile)
+      bf16* pk1 = pk + PK_FC1 + (nt * 16 + rq) * F0P + ft * 16 + n16;   // [n][F0P f]
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (idx[r] >= 0) sgd_apply(idx[r], acc[r], p[r], m[r], params, mom, pk, lr, momentum, wd);
+        if (idx[r] >= 0)
+          pk1[r * F0P] = (bf16)sgd_update(idx[r], acc[r], p[r], m[r], params, mom, lr, momentum, wd);
       FEDMI_STAMP(3, 3);
     }
   } else if (b < SGD_NA + SGD2_NB + SGD2_NC) {        // fc2.weight [84][120]: 6 x 8 tiles
@@ -1295,9 +1364,16 @@ __global__ __launch_bounds__(256) void lenet_sgd2(
       }
       const f32x4 acc = batch_tile(dz2t + (size_t)nt * 16 * MAX_TRAIN_BATCH, h1T + (size_t)ft * 16 * MAX_TRAIN_BATCH, nb,
                                    params, mom, idx, p, m);
+      const int n0 = nt * 16 + rq, f = ft * 16 + n16;
+      bf16* pk2 = pk + PK_FC2 + n0 * 128 + f;       // [n][128 f]
+      bf16* pk2t = pk + PK_FC2T + f * 96 + n0;      // [f][96 n]
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (idx[r] >= 0) sgd_apply(idx[r], acc[r], p[r], m[r], params, mom, pk, lr, momentum, wd);
+        if (idx[r] >= 0) {
+          const bf16 v = (bf16)sgd_update(idx[r], acc[r], p[r], m[r], params, mom, lr, momentum, wd);
+          pk2[r * 128] = v;
+          pk2t[r] = v;
+        }
     }
   } else if (b < SGD_NA + SGD2_NB + SGD2_NC + SGD2_ND) {   // fc3.weight [10][84]: 1 x 6 tiles
     const int t = (b - SGD_NA - SGD2_NB - SGD2_NC) * 4 + wave;
@@ -1312,9 +1388,11 @@ __global__ __launch_bounds__(256) void lenet_sgd2(
         idx[r] = (n < NCLS && f < F2) ? P_F3W + n * F2 + f : -1;
       }
       const f32x4 acc = batch_tile(dz3t, h2t + (size_t)t * 16 * MAX_TRAIN_BATCH, nb, params, mom, idx, p, m);
+      bf16* pk3 = pk + PK_FC3 + rq * 96 + t * 16 + n16;   // [n][96 f]
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (idx[r] >= 0) sgd_apply(idx[r], acc[r], p[r], m[r], params, mom, pk, lr, momentum, wd);
+        if (idx[r] >= 0)
+          pk3[r * 96] = (bf16)sgd_update(idx[r], acc[r], p[r], m[r], params, mom, lr, momentum, wd);
     }
   } else {                                            // FC biases + loss / accuracy counters
     // block e < 4: biases [64e, 64e + 64) x 4 sample groups of 32 (all 32 loads in flight),
@@ -1354,11 +1432,24 @@ __global__ __launch_bounds__(256) void lenet_sgd2(
     __syncthreads();
     if (e < SGD2_NE && g == 0 && j < 214) {
       const float sum = (bsum[0][tid] + bsum[1][tid]) + (bsum[2][tid] + bsum[3][tid]);
-      sgd_apply(bi, sum, bp, bm, params, mom, pk, lr, momentum, wd);
+      sgd_update(bi, sum, bp, bm, params, mom, lr, momentum, wd);   // biases have no packed image
     }
   }
   if (b == 0 && tid == 0 && round_ctr) atomicAdd(round_ctr, 1);
   FEDMI_STAMP(3, 1);
+}
+
+// The prepared images of one batch in a launch of their own: an epoch's first step and the eager step
+// (every other batch of an epoch is prepared by the KS2 launch in front of its KS1).
+__global__ __launch_bounds__(PREP_NT) void lenet_prep_batch(
+    const uint8_t* __restrict__ images, int sample_base, int nb, uint32_t seed,
+    const int* __restrict__ round_ctr, int augment, bf16* __restrict__ xprep)
+{
+  __shared__ __attribute__((aligned(16))) uint8_t raw[IMG_BYTES];
+  const int sp = blockIdx.x / PREP_SPLIT;
+  if (sp >= nb) return;
+  prep_sample(images, sample_base + sp, blockIdx.x - sp * PREP_SPLIT, seed, round_ctr, augment,
+              xprep + (size_t)sp * XP_ELEMS, raw);
 }
 
 // ---------------------------------------------------------------------------
@@ -1451,20 +1542,36 @@ void launch_lenet_pack(hipStream_t st, const float* params, bf16* pk) {
   hipLaunchKernelGGL(lenet_pack, dim3((P_TOTAL + 255) / 256), dim3(256), 0, st, params, pk);
 }
 
-void launch_lenet_sample_step(hipStream_t st, const uint8_t* images, int sample_base, int nb, const bf16* pk,
-                              const float* params, uint32_t seed, const int* round_ctr, int augment,
-                              const int* labels, bf16* act2T, bf16* h1T, float* aux, bf16* dZ1T, float* conv_slab) {
-  if (nb <= 0 || nb > MAX_TRAIN_BATCH) throw std::invalid_argument("lenet_sample_step: batch must be in [1, 128]");
-  hipLaunchKernelGGL(lenet_sample_step, dim3(nb), dim3(NT_CONV), 0, st, images, sample_base, nb, pk, params, seed,
-                     round_ctr, augment, labels, act2T, h1T, reinterpret_cast<unsigned char*>(aux), dZ1T, conv_slab);
+void launch_lenet_prep_batch(hipStream_t st, const uint8_t* images, int sample_base, int nb, uint32_t seed,
+                             const int* round_ctr, int augment, bf16* xprep) {
+  if (nb <= 0 || nb > MAX_TRAIN_BATCH) throw std::invalid_argument("lenet_prep_batch: batch must be in [1, 128]");
+  if (sample_base < 0) throw std::invalid_argument("lenet_prep_batch: negative first sample");
+  hipLaunchKernelGGL(lenet_prep_batch, dim3(nb * PREP_SPLIT), dim3(PREP_NT), 0, st, images, sample_base, nb, seed,
+                     round_ctr, augment, xprep);
 }
 
+void launch_lenet_sample_step(hipStream_t st, const bf16* xprep, int nb, const bf16* pk, const float* params,
+                              const int* labels, bf16* act2T, bf16* h1T, float* aux, bf16* dZ1T, float* conv_slab) {
+  if (nb <= 0 || nb > MAX_TRAIN_BATCH) throw std::invalid_argument("lenet_sample_step: batch must be in [1, 128]");
+  hipLaunchKernelGGL(lenet_sample_step, dim3(nb), dim3(NT_CONV), 0, st, xprep, nb, pk, params, labels, act2T, h1T,
+                     reinterpret_cast<unsigned char*>(aux), dZ1T, conv_slab);
+}
+
+// next_nb > 0: the launch also prepares the images of samples [next_base, next_base + next_nb) for the KS1
+// behind it.  Never together with a round-counter bump: the prepared batch would race the counter it reads.
 void launch_lenet_sgd2(hipStream_t st, float* params, float* mom, bf16* pk, const float* conv_slab, int nb,
                        const bf16* act2T, const bf16* h1T, const float* aux, const bf16* dZ1T, float lr,
-                       float momentum, float wd, int* round_ctr, Stats* stats) {
+                       float momentum, float wd, int* round_ctr, Stats* stats, const uint8_t* images, int next_base,
+                       int next_nb, uint32_t seed, const int* aug_ctr, int augment, bf16* xprep) {
   if (nb <= 0 || nb > MAX_TRAIN_BATCH) throw std::invalid_argument("lenet_sgd2: batch must be in [1, 128]");
-  hipLaunchKernelGGL(lenet_sgd2, dim3(SGD2_GRID), dim3(256), 0, st, params, mom, pk, conv_slab, nb, act2T, h1T,
-                     reinterpret_cast<const unsigned char*>(aux), dZ1T, lr, momentum, wd, round_ctr, stats);
+  if (next_nb < 0 || next_nb > MAX_TRAIN_BATCH || (next_nb > 0 && next_base < 0))
+    throw std::invalid_argument("lenet_sgd2: next batch must be in [0, 128]");
+  if (next_nb > 0 && round_ctr != nullptr)
+    throw std::invalid_argument("lenet_sgd2: the launch that bumps the round counter prepares no batch");
+  static_assert(PREP_NT == 256, "prep blocks are KS2 blocks");
+  hipLaunchKernelGGL(lenet_sgd2, dim3(SGD2_GRID + next_nb * PREP_SPLIT), dim3(256), 0, st, params, mom, pk, conv_slab,
+                     nb, act2T, h1T, reinterpret_cast<const unsigned char*>(aux), dZ1T, lr, momentum, wd, round_ctr,
+                     stats, images, next_base, next_nb, seed, aug_ctr, augment, xprep);
 }
 
 }  // namespace fedmi

@@ -62,6 +62,12 @@ constexpr int PK_FC2T = PK_FC2 + 96 * 128;      // [128 f][96 n]       fc2 dgrad
 constexpr int PK_FC3  = PK_FC2T + 128 * 96;     // [16 n][96 f]        fc3 fwd + dgrad (KS1 stages it in LDS)
 constexpr int PK_TOTAL = PK_FC3 + 16 * 96;
 
+// ---- prepared training images (written a step ahead, read by KS1's stage) ----
+// One batch of augmented, normalised images as KS1 wants them in LDS: channels-last bf16 [36 y][40 x][4 c],
+// rows 32..35, columns 32..39 and channel 3 zero.  11,520 B per sample.
+constexpr int XP_H = 36, XP_W = 40, XP_C = 4;
+constexpr int XP_ELEMS = XP_H * XP_W * XP_C;    // 5760 bf16 per sample
+
 // ---- training-step geometry -------------------------------------------------
 constexpr int MAX_TRAIN_BATCH = 128;     // reference batch (src/main.py:140)
 constexpr int FC_SPW = 16;               // samples per eval FC-head workgroup (one MFMA row tile)

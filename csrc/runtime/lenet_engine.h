@@ -33,6 +33,7 @@ struct LeNetBuffers {
   lenet::Stats* train_stats = nullptr;
   lenet::Stats* eval_stats = nullptr;
   int* round_ctr = nullptr;      // augmentation epoch counter (device)
+  bf16* xprep = nullptr;         // [MAX_TRAIN_BATCH][XP_ELEMS]  the next KS1's augmented images (prep / KS2 -> KS1)
 };
 
 struct SgdConfig {
@@ -50,7 +51,8 @@ class LeNetEngine {
   void set_schedule(const std::vector<int>& starts, const std::vector<int>& sizes);
   int schedule_len() const { return (int)starts_.size(); }
 
-  // One SGD step (eager launches: KS1 lenet_sample_step + KS2 lenet_sgd2) on samples [start, start+nb).
+  // One SGD step (eager launches: lenet_prep_batch + KS1 lenet_sample_step + KS2 lenet_sgd2) on samples
+  // [start, start+nb).
   void step(hipStream_t st, int start, int nb, bool bump_round, bool reset_stats = false);
   // One local epoch over the schedule; graph replay when use_graph.
   void run_epoch(hipStream_t st, bool use_graph);
@@ -63,6 +65,9 @@ class LeNetEngine {
 
  private:
   void enqueue_epoch(hipStream_t st);
+  void check_batch(int start, int nb, const char* what) const;
+  void prep(hipStream_t st, int start, int nb);
+  void launch_step(hipStream_t st, int start, int nb, bool bump_round, int next_start, int next_nb);
   void drop_graph();
 
   LeNetBuffers b_;

@@ -3,7 +3,9 @@
 Device memory is allocated through PyTorch (caching allocator) and handed to
 ``_fedmi_native.LeNetEngine`` as raw pointers.  Per round the host issues:
 one graph launch (the whole local epoch: 2 kernels x #owned batches -- KS1
-``lenet_sample_step`` and KS2 ``lenet_sgd2``, csrc/kernels/lenet_kernels.hip), the
+``lenet_sample_step`` and KS2 ``lenet_sgd2``, which also augments the next batch's
+images into ``xprep``; ``lenet_prep_batch`` does that for the first batch --
+csrc/kernels/lenet_kernels.hip), the
 FedAvg all-reduce on :meth:`float_state`, one pack launch, and three eval
 launches — no per-step host synchronisation (the reference syncs twice per
 step via ``.item()``, src/main.py:153-156).
@@ -72,13 +74,14 @@ class LeNetNativeTrainer(LocalTrainer):
             self.eval_part = z(2 * ((self.act2_rows + L["FC_SPW"] - 1) // L["FC_SPW"]))
             self.stats = z(2, 4, dt=torch.int32)       # [train, eval] x {loss_f32, correct, count, pad}
             self.round_ctr = z(4, dt=torch.int32)
+            self.xprep = z(B, L["XP_ELEMS"], dt=torch.bfloat16)         # prep / KS2 -> KS1: the next batch's images
         self._bufs = dict(
             train_images=_ptr(self.train_set.x), train_labels=_ptr(self.train_set.y), n_train=len(self.train_set),
             params=_ptr(self.params), mom=_ptr(self.mom), pk=_ptr(self.pk), act2=_ptr(self.act2),
             act2_rows=self.act2_rows, act2T=_ptr(self.act2T), h1=_ptr(self.h1), dact2=_ptr(self.dact2),
             dZ1T=_ptr(self.dZ1T), conv_slab=_ptr(self.conv_slab), eval_part=_ptr(self.eval_part),
             eval_part_floats=self.eval_part.numel(), train_stats=_ptr(self.stats[0]),
-            eval_stats=_ptr(self.stats[1]), round_ctr=_ptr(self.round_ctr))
+            eval_stats=_ptr(self.stats[1]), round_ctr=_ptr(self.round_ctr), xprep=_ptr(self.xprep))
         self.engine = nat.LeNetEngine(self._bufs, cfg.lr, cfg.momentum, cfg.weight_decay, cfg.seed & 0xFFFFFFFF,
                                       bool(data.augment and cfg.augment))
         self._views = ordered_views(self.params, LENET_SPEC)

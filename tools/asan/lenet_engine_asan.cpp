@@ -72,6 +72,7 @@ int main() {
   b.train_stats = stats;
   b.eval_stats = stats + 1;
   b.round_ctr = dalloc<int>(4);
+  b.xprep = dalloc<bf16>((size_t)MAX_TRAIN_BATCH * XP_ELEMS);
 
   // small random weights
   std::vector<float> p0(P_TOTAL);
@@ -81,6 +82,11 @@ int main() {
   hipStream_t st;
   check_hip(hipStreamCreate(&st), "stream");
   {
+    {                                  // a buffer set without the prepared-image buffer is rejected
+      LeNetBuffers nb = b;
+      nb.xprep = nullptr;
+      try { LeNetEngine bad(nb, SgdConfig{}, 7u, true); expect(false, "missing xprep accepted"); } catch (const std::invalid_argument&) {}
+    }
     LeNetEngine eng(b, SgdConfig{}, 7u, true);
     eng.pack(st);
     // error paths

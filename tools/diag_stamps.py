@@ -3,7 +3,11 @@
 Run with FEDMI_NATIVE_VARIANT=stamps (the -DFEDMI_STAMPS extension).  Executes a
 few warm-up steps, then one eager step of 128 samples, and prints, per kernel,
 the median (and max) cycles each workgroup spent in every phase, plus the
-spread of workgroup start times.
+spread of workgroup start times.  An eager step's KS2 prepares no next batch,
+so a two-step epoch follows: the prep workgroups of its first KS2 keep their
+stamps (the second KS2 has none) and their own durations are printed next to
+the FC tiles' (stamps of different workgroups may come from different XCDs'
+counters, so only a workgroup's own differences are meaningful).
 """
 import os
 import sys
@@ -38,7 +42,7 @@ def main():
     if True:   # KS1 + KS2 (the only training path)
         # KS1: forward slots 0..6 under kernel 0, its backward slots 2..5 under kernel 2; KS2 under kernel 3
         ks1 = np.concatenate([st[0, :128, :7], st[2, :128, 2:6]], axis=1)
-        phases = ["stage+zero+aug", "conv1", "pool1", "conv2|shift build", "pool2 barrier", "fc fwd+bwd", "dY2 scatter",
+        phases = ["stage+zero", "conv1", "pool1", "conv2|shift build", "pool2 barrier", "fc fwd+bwd", "dY2 scatter",
                   "c2 wgrad+dgrad", "c1 wgrad", "slab store"]
         a = ks1[ks1[:, 0] > 0]
         d = np.diff(a, axis=1)
@@ -79,6 +83,18 @@ def main():
         if len(f1):
             print(f"    sgd2 fc1 split: start->operands+MFMA med {np.median(f1[:, 2] - f1[:, 0]):8.0f}  "
                   f"SGD stores issued med {np.median(f1[:, 3] - f1[:, 2]):8.0f}  -> end med {np.median(f1[:, 1] - f1[:, 3]):8.0f}")
+    # prep workgroups of KS2 (blocks >= 249, 3 per sample): a two-step eager epoch; KS2(0) prepares batch 1
+    nat.read_stamps(True)
+    tr.cfg.use_graph = False
+    tr.set_schedule([0, 128], [128, 128])
+    tr.train_epoch()
+    torch.cuda.synchronize()
+    st2 = np.frombuffer(nat.read_stamps(True), dtype=np.uint64).reshape(nat.STAMP_SHAPE).astype(np.int64)
+    pr = st2[3, 249:249 + 3 * 128, :2]
+    pr = pr[pr[:, 0] > 0]
+    if len(pr):
+        d = pr[:, 1] - pr[:, 0]
+        print(f"    sgd2 prep next  wgs={len(pr):4d} med {np.median(d):8.0f}  max {d.max():8.0f}")
     for k, (name, phases) in names.items():
         a = st[k, :nwg[k], :len(phases) + 1]
         a = a[a[:, 0] > 0]
