@@ -23,6 +23,13 @@ Ops without a native implementation are counted in :attr:`NativeMode.fallbacks`
 (and raise with ``strict=True``): the GPU tests assert that a training step of
 every hybrid family needs none.
 
+This module holds the op table, the conv routing and the mode.  The launchers under every impl (``ew``,
+``fill_``, ``reduce_sum``, the op codes) are :mod:`fedmi.ops.zoo_launch`; the peephole fusions' state -- a result
+whose pass is still pending, and which op may consume it -- is :mod:`fedmi.ops.zoo_fusion`.  A producer impl
+hands the mode a pending result (:meth:`NativeMode.pend`); before the next op the mode asks it once whether that
+op joins, and the consuming impl takes the claim (:meth:`NativeMode.take`); what nobody takes is materialised
+before anything, ATen included, can read it.
+
 Reference ops: the union of SURVEY.md §2.4(d) (convolution(+backward), addmm/mm,
 native_batch_norm(+backward), relu / threshold_backward, avg_pool2d, cat,
 max_pool2d_with_indices, sigmoid, mul, mean, slice_backward, bernoulli_, ...).
@@ -32,7 +39,6 @@ from __future__ import annotations
 import collections
 import sys
 import os
-import math
 from typing import Optional
 
 import torch
@@ -40,131 +46,30 @@ import torch.nn.functional as F
 from torch.overrides import TorchFunctionMode
 from torch.utils._python_dispatch import TorchDispatchMode
 
-from .. import native
 from . import conv as CV
+from .zoo_fusion import (_CatBuf, _PendingBN, _PendingBNB, _PendingCtr, _PendingMul, _PendingSliceBwd, _PendingThr,
+                         _sb_pair)
+from .zoo_launch import (EW_ADD, EW_ADDS, EW_BERN, EW_BNB, EW_BNB_ADD, EW_BNB_THR, EW_BNB_THR_ADD,  # noqa: F401
+                         EW_COPY, EW_DIV, EW_FILL, EW_FMA, EW_FMA_ADD, EW_FMA_ADD_RELU, EW_FMA_RELU, EW_MUL, EW_MULS,
+                         EW_RELU, EW_SIG_BWD, EW_SIGMOID, EW_SUB, EW_THR_BWD, RD_DOT_R, RD_DOT_SHIFT, RD_SUM,
+                         RD_SUMSQ_SHIFT, _DT, _cl_rows, _nat, _row_stride, _rowmajor_out, _rows_ld, _same, _st,
+                         current_mode, ew, fill_, reduce_sum, set_current_mode, zd)
 
 aten = torch.ops.aten
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.int64: 2}
-
-# elementwise op codes (zoo_ops.hip EwOp)
-EW_COPY, EW_ADD, EW_MUL, EW_MULS, EW_RELU, EW_THR_BWD, EW_SIGMOID, EW_SIG_BWD, EW_FILL, EW_FMA = range(10)
-EW_BNB, EW_BERN, EW_SUB, EW_DIV, EW_ADDS, EW_FMA_RELU, EW_BNB_THR = 11, 12, 13, 14, 15, 16, 17
-EW_FMA_ADD, EW_FMA_ADD_RELU, EW_BNB_ADD, EW_BNB_THR_ADD = 18, 19, 20, 21
 # an impl returns ATEN when the op is legitimately ATen's (host copies, scalar reads): not a fallback
 ATEN = object()
-RD_SUM, RD_SUMSQ_SHIFT, RD_DOT_SHIFT, RD_DOT_R = 0, 1, 2, 3
 
 
-def _nat():
-    return native.require()
+def _take(cls):
+    """(pending result, its join answer) of kind ``cls`` that the running op claimed, or (None, None)."""
+    mode = current_mode()
+    return mode.take(cls) if mode is not None else (None, None)
 
 
-def _st(dev) -> int:
-    return native.stream_handle(dev)
+def _ptr(t: Optional[torch.Tensor]) -> int:
+    return 0 if t is None else t.data_ptr()
 
-
-def zd(t: Optional[torch.Tensor]):
-    """(ptr, dtype code, sizes, strides) descriptor of a CUDA tensor (None passes through)."""
-    if t is None:
-        return None
-    if t.dtype not in _DT:
-        raise TypeError(f"native_mode: unsupported dtype {t.dtype}")
-    if t.numel() >= (1 << 31):
-        raise ValueError("native_mode: tensors must have < 2^31 elements")
-    if t.dim() == 0:
-        return (t.data_ptr(), _DT[t.dtype], [1], [1])
-    return (t.data_ptr(), _DT[t.dtype], list(t.shape), list(t.stride()))
-
-
-def _bcast(t: torch.Tensor, shape) -> torch.Tensor:
-    if tuple(t.shape) == tuple(shape):
-        return t
-    return t.expand(shape) if t.dim() == len(shape) else t.reshape((1,) * (len(shape) - t.dim()) + tuple(t.shape)).expand(shape)
-
-
-def coalesce(shape, strides):
-    """Merge the dims of an iteration space shared by several operands (``strides``: one stride list per
-    operand, operand 0 decides the order): size-1 dims drop, dims are ordered by operand 0's strides and
-    neighbours that are contiguous in EVERY operand merge -- a channels-last activation with a
-    per-channel operand becomes [N*H*W, C], a pure elementwise op one flat dim."""
-    dims = [d for d in range(len(shape)) if shape[d] != 1]
-    if not dims:
-        return [1], [[0] for _ in strides]
-    dims.sort(key=lambda d: -abs(strides[0][d]))
-    nshape = [shape[dims[0]]]
-    nstr = [[s[dims[0]]] for s in strides]
-    for d in dims[1:]:
-        if all(ns[-1] == s[d] * shape[d] for ns, s in zip(nstr, strides)):
-            nshape[-1] *= shape[d]
-            for ns, s in zip(nstr, strides):
-                ns[-1] = s[d]
-        else:
-            nshape.append(shape[d])
-            for ns, s in zip(nstr, strides):
-                ns.append(s[d])
-    return nshape, nstr
-
-
-def ew(out: torch.Tensor, ins, op: int, s0: float = 0.0, s1: float = 0.0, seed: int = 0, ctr=None) -> torch.Tensor:
-    """out[...] = op(ins...) with broadcasting of every input to out's shape."""
-    if out.numel() == 0:
-        return out
-    if out.numel() >= (1 << 31):
-        raise ValueError("native_mode: tensors must have < 2^31 elements")
-    shape = list(out.shape) if out.dim() else [1]
-    o = out if out.dim() else out.view(1)
-    ts = [_bcast(t if t.dim() else t.view(1), shape) for t in ins]
-    for t in ts:
-        if t.dtype not in _DT:
-            raise TypeError(f"native_mode: unsupported dtype {t.dtype}")
-    if op == EW_BERN:
-        # the counter-based mask is a function of the logical element index: keep the logical order
-        nshape, nstr = shape, [list(o.stride())] + [list(t.stride()) for t in ts]
-    else:
-        nshape, nstr = coalesce(shape, [list(o.stride())] + [list(t.stride()) for t in ts])
-    allt = [o] + ts
-    vw, vmask = 8, -1
-    if op != EW_BERN:
-        for vw in (8, 4):
-            vmask = _vec_mask(nshape, nstr, allt, vw)
-            if vmask >= 0:
-                break
-    if vmask >= 0:
-        nshape = nshape[:-1] + [nshape[-1] // vw]
-        nstr = [st[:-1] + [st[-1] * vw] for st in nstr]
-    if NativeMode.current is not None and NativeMode.current.diag:   # passes per op code, and which miss the vector launch
-        NativeMode.current.ew_ops[(NativeMode.current._func_name(), op)] += 1
-        if vmask < 0:
-            NativeMode.current.scalar_ew[(op, tuple(out.shape), tuple(out.stride()),
-                                          tuple(tuple(t.stride()) for t in ts))] += 1
-    descs = [(t.data_ptr(), _DT[t.dtype], nshape, st) for t, st in zip(allt, nstr)]
-    _nat().z_ew(_st(out.device), descs[0], descs[1:], op, float(s0), float(s1), int(seed) & 0xFFFFFFFF,
-                0 if ctr is None else ctr.data_ptr(), vmask, vw)
-    return out
-
-
-def _vec_mask(shape, strides, ts, vw: int = 8) -> int:
-    """Bit k (input k) set if that operand is contiguous over groups of ``vw`` innermost elements, bit
-    clear = a broadcast operand; -1 = the vector launch does not apply (odd sizes, misalignment,
-    int64, an output that is not unit-stride innermost, fp32 with vw 4 below 16-byte alignment)."""
-    if shape[-1] % vw:
-        return -1
-    mask = 0
-    for k, (t, st) in enumerate(zip(ts, strides)):
-        inner = st[-1]
-        if inner == 0 and k > 0:
-            continue
-        align = 16 if (t.dtype == torch.float32 or vw == 8) else 8
-        if inner != 1 or t.dtype == torch.int64 or t.data_ptr() % align or any(v % vw for v in st[:-1]):
-            return -1
-        if k > 0:
-            mask |= 1 << (k - 1)
-    return mask
-
-
-def fill_(t: torch.Tensor, v: float) -> torch.Tensor:
-    return ew(t, [], EW_FILL, v)
 
 
 def _scalar(x) -> Optional[float]:
@@ -203,85 +108,6 @@ def _dev(*ts):
     return None
 
 
-def _rowmajor_out(out: torch.Tensor) -> bool:
-    """out's elements sit at their row-major index (size-1 dims ignored): a reduction can store into it by the
-    accumulator index."""
-    if out.dtype not in (torch.float32, torch.bfloat16):
-        return False
-    expect = 1
-    for d in range(out.dim() - 1, -1, -1):
-        if out.shape[d] == 1:
-            continue
-        if out.stride(d) != expect:
-            return False
-        expect *= out.shape[d]
-    return True
-
-
-def reduce_sum(a: torch.Tensor, dims, acc: Optional[torch.Tensor], op: int = RD_SUM, b: Optional[torch.Tensor] = None,
-               shift: Optional[torch.Tensor] = None, acc2: Optional[torch.Tensor] = None,
-               out: Optional[torch.Tensor] = None, scale: float = 1.0) -> None:
-    """acc (fp32, ZEROED, one entry per kept element in order) += sum over ``dims`` of f(a[, b]); or, with
-    ``out`` (RD_SUM, :func:`_rowmajor_out`), out = scale * sum stored directly (no zeroed accumulator, no copy:
-    the bias gradients, spatial means of SE gates, sums of autograd's broadcast backward)."""
-    dims = sorted(d % a.dim() for d in dims)
-    kept = [d for d in range(a.dim()) if d not in dims]
-    ops = [a] if b is None else [a, b]
-
-    def space(ds, order_by_acc):
-        if not ds:
-            return [1], [[0] for _ in ops]
-        shp = [a.shape[d] for d in ds]
-        strs = [[t.stride(d) for d in ds] for t in ops]
-        if order_by_acc:
-            # kept dims: the accumulator index is row-major over them -- merge only, never reorder
-            acc_str = [1] * len(ds)
-            for j in range(len(ds) - 2, -1, -1):
-                acc_str[j] = acc_str[j + 1] * shp[j + 1]
-            ns, nst = coalesce(shp, [acc_str] + strs)
-            return ns, nst[1:]
-        return coalesce(shp, strs)
-
-    oshape, ostr = space(kept, True)
-    ishape, istr = space(dims, False)
-    if op != RD_DOT_R and _rows_ok(oshape, ostr, ishape, istr, ops):
-        # channels-last moments / bias gradients: [M, C] rows, 16-byte channel vectors, deterministic
-        C, M = oshape[0], ishape[0]
-        nat = _nat()
-        part = torch.empty(int(nat.z_reduce_rows_ws_floats(M, C)), dtype=torch.float32, device=a.device)
-        nat.z_reduce_rows(_st(a.device), a.data_ptr(), _DT[a.dtype], istr[0][0],
-                          b.data_ptr() if b is not None else 0, _DT[b.dtype] if b is not None else 0,
-                          istr[1][0] if b is not None else 0, shift.data_ptr() if shift is not None else 0, C, M, op,
-                          part.data_ptr(), part.numel(), acc.data_ptr() if acc is not None else 0,
-                          acc2.data_ptr() if acc2 is not None else 0, out.data_ptr() if out is not None else 0,
-                          _DT[out.dtype] if out is not None else 0, float(scale))
-        return
-    outer = (0, 0, oshape, ostr[0])
-    inner = (0, 0, ishape, istr[0])
-    outer_b = (0, 0, oshape, ostr[1]) if b is not None else None
-    inner_b = (0, 0, ishape, istr[1]) if b is not None else None
-    nat = _nat()
-    # split partials summed in a fixed order afterwards (no float atomics: bitwise-reproducible steps)
-    nws = int(nat.z_reduce_ws_floats(math.prod(oshape), math.prod(ishape)))
-    part = torch.empty(max(nws, 1), dtype=torch.float32, device=a.device)
-    nat.z_reduce(_st(a.device), outer, inner, outer_b, inner_b, a.data_ptr(), _DT[a.dtype],
-                 b.data_ptr() if b is not None else 0, _DT[b.dtype] if b is not None else 0,
-                 shift.data_ptr() if shift is not None else 0, acc.data_ptr() if acc is not None else 0,
-                 acc2.data_ptr() if acc2 is not None else 0, op, part.data_ptr(), nws,
-                 out.data_ptr() if out is not None else 0, _DT[out.dtype] if out is not None else 0, float(scale))
-
-
-def _rows_ok(oshape, ostr, ishape, istr, ops) -> bool:
-    if len(oshape) != 1 or len(ishape) != 1 or oshape[0] % 4 or ishape[0] < 1:
-        return False
-    vw = 8 if oshape[0] % 8 == 0 else 4
-    for t, os_, is_ in zip(ops, ostr, istr):
-        align = 16 if (t.dtype == torch.float32 or vw == 8) else 8
-        if os_[0] != 1 or is_[0] % vw or t.dtype not in (torch.float32, torch.bfloat16) or t.data_ptr() % align:
-            return False
-    return True
-
-
 # ---------------------------------------------------------------------------- op impls
 _IMPL = {}
 
@@ -297,17 +123,8 @@ def impl(*ops):
 # ---- elementwise ---------------------------------------------------------------
 @impl(aten.add.Tensor, aten.sub.Tensor)
 def _add(func, self, other, alpha=1):
-    mode = NativeMode.current
-    if func is aten.add.Tensor and alpha == 1 and mode is not None and mode._pend_bn is not None:
-        pend = mode._pend_bn
-        res = _bn_add_partner(pend, (self, other))
-        if res is not None:         # BN(x) + shortcut joins the pending apply pass; the BN output stays deferred
-            out = torch.empty_like(pend.out)
-            mode._pend_bn = _PendingBN(out, pend.x, pend.scale, pend.shift, res)
-            mode._defer(pend.out, pend.materialize)
-            mode.fused["bn+add"] += 1
-            return out
-    pair = _sb_pair(mode, (self, other), {"alpha": alpha}) if func is aten.add.Tensor else None
+    mode = current_mode()
+    pair = mode.take_pair() if mode is not None else None
     if pair is not None:            # slice_backward(g1, [0, a)) + slice_backward(g2, [a, n)): two copies
         lo, hi = pair
         out = torch.empty_like(lo.out)
@@ -315,15 +132,20 @@ def _add(func, self, other, alpha=1):
         ew(out.narrow(hi.dim, hi.start, hi.end - hi.start), [hi.grad], EW_COPY)
         mode.fused["slice_bwd+add"] += 1
         return out
-    if func is aten.add.Tensor and mode is not None and mode._pend_bnb is not None:
-        o = _bnb_add_partner(mode._pend_bnb, (self, other), {"alpha": alpha})
-        if o is not None:           # BN-backward gradient + the other incoming gradient: one pass
-            pend, mode._pend_bnb = mode._pend_bnb, None
-            out = _alloc_like_meta(func, (self, other), {"alpha": alpha}, self.device)
-            pend.add(out, o)
-            mode._defer(pend.out, pend.materialize)
-            mode.fused["bn_bwd+grad_add"] += 1
-            return out
+    pend, res = _take(_PendingBN)
+    if pend is not None:            # BN(x) + shortcut joins the pending apply pass; the BN output stays deferred
+        out = torch.empty_like(pend.out)
+        mode.pend(_PendingBN(out, pend.x, pend.scale, pend.shift, res))
+        mode._defer(pend)
+        mode.fused["bn+add"] += 1
+        return out
+    pend, o = _take(_PendingBNB)
+    if pend is not None:            # BN-backward gradient + the other incoming gradient: one pass
+        out = _alloc_like_meta(func, (self, other), {"alpha": alpha}, self.device)
+        pend.add(out, o)
+        mode._defer(pend)
+        mode.fused["bn_bwd+grad_add"] += 1
+        return out
     sign = -1.0 if func is aten.sub.Tensor else 1.0
     s = _scalar(other)
     if s is not None:
@@ -336,40 +158,24 @@ def _add(func, self, other, alpha=1):
 def _add_(func, self, other, alpha=1):
     sign = -1.0 if func is aten.sub_.Tensor else 1.0
     s = _scalar(other)
-    mode = NativeMode.current
+    mode = current_mode()
     if (s is not None and mode is not None and mode.fuse and func is aten.add_.Tensor and sign * alpha * s == 1.0
             and self.dtype == torch.int64 and self.numel() == 1):
         # BatchNorm's num_batches_tracked += 1 (torch.nn.modules.batchnorm, right before the batch_norm call): the
         # BN forward's finalizing workgroup bumps it, so it costs no launch of its own
-        mode._flush_ctr()
-        mode._pend_ctr = self
+        mode.pend(_PendingCtr(self))
         mode.fused["bn_counter"] += 1
         return self
-    if func is aten.add_.Tensor and mode is not None and mode._pend_bnb is not None:
-        o = _bnb_add_partner(mode._pend_bnb, (self, other), {"alpha": alpha})
-        if o is not None:           # in-place accumulation into either operand: one pass
-            pend, mode._pend_bnb = mode._pend_bnb, None
-            pend.add(self, o)
-            if o is self:
-                mode._defer(pend.out, pend.materialize)
-            mode.fused["bn_bwd+grad_add"] += 1
-            return self
+    pend, o = _take(_PendingBNB)
+    if pend is not None:            # in-place accumulation into either operand: one pass
+        pend.add(self, o)
+        if o is self:
+            mode._defer(pend)
+        mode.fused["bn_bwd+grad_add"] += 1
+        return self
     if s is not None:
         return ew(self, [self], EW_ADDS, sign * alpha * s)
     return ew(self, [self, other], EW_ADD, sign * alpha)
-
-
-class _PendingMul:
-    """a * b (same shapes) not computed yet: if the next op sums it over some dims (autograd's backward of a
-    broadcast multiply -- the SE gate's gradient), the product is folded into that reduction (RD_DOT_SHIFT,
-    no shift) and never stored; any other op materialises it."""
-    __slots__ = ("out", "a", "b")
-
-    def __init__(self, out, a, b):
-        self.out, self.a, self.b = out, a, b
-
-    def materialize(self):
-        ew(self.out, [self.a, self.b], EW_MUL)
 
 
 @impl(aten.mul.Tensor)
@@ -381,10 +187,10 @@ def _mul(func, self, other):
     if s is not None:
         return ew(torch.empty_like(other), [other], EW_MULS, s)
     out = _alloc_like_meta(func, (self, other), {}, _dev(self, other))
-    mode = NativeMode.current
+    mode = current_mode()
     if (mode is not None and mode.fuse and self.shape == other.shape == out.shape and self.dtype == other.dtype
             and out.dim() >= 2):
-        mode._pend_mul = _PendingMul(out, self, other)
+        mode.pend(_PendingMul(out, self, other))
         return out
     return ew(out, [self, other], EW_MUL)
 
@@ -423,74 +229,32 @@ def _div_t(func, self, other):
 
 @impl(aten.relu.default)
 def _relu(func, self):
-    pend = _mode_pending_bn(self)
+    pend, _ = _take(_PendingBN)
     if pend is not None:            # relu(BN(x) [+ res]) in ONE pass; the pre-ReLU tensor stays deferred (dead)
         out = torch.empty_like(self)
         pend.relu(out)
-        NativeMode.current._defer(self, pend.materialize)
-        NativeMode.current.fused["bn+relu" if pend.res is None else "bn+add+relu"] += 1
+        current_mode()._defer(pend)
+        current_mode().fused["bn+relu" if pend.res is None else "bn+add+relu"] += 1
         return out
     return ew(torch.empty_like(self), [self], EW_RELU)
 
 
 @impl(aten.relu_.default)
 def _relu_(func, self):
-    pend = _mode_pending_bn(self)
+    pend, _ = _take(_PendingBN)
     if pend is not None:            # the pending output is overwritten by its ReLU: one pass, nothing deferred
-        NativeMode.current.fused["bn+relu_" if pend.res is None else "bn+add+relu_"] += 1
+        current_mode().fused["bn+relu_" if pend.res is None else "bn+add+relu_"] += 1
         return pend.relu(self)
     return ew(self, [self], EW_RELU)
-
-
-class _PendingBNB:
-    """A BatchNorm input gradient whose apply pass has not run: when autograd next sums it with the tensor's
-    other incoming gradient (DenseNet: the concat's slice; residual nets: the shortcut), the sum joins the
-    pass (EW_BNB[_THR]_ADD, the gradient rounded as the unfused pair stores it); any other op materialises it."""
-    __slots__ = ("out", "ins", "thr")
-
-    def __init__(self, out, ins, thr):
-        self.out, self.ins, self.thr = out, ins, thr
-
-    def materialize(self):
-        ew(self.out, self.ins, EW_BNB_THR if len(self.ins) == 6 else EW_BNB, self.thr)
-
-    def add(self, out, other):
-        rnd = 1.0 if self.out.dtype == torch.bfloat16 else 0.0
-        return ew(out, self.ins + [other], EW_BNB_THR_ADD if len(self.ins) == 6 else EW_BNB_ADD, self.thr, rnd)
-
-
-def _bnb_add_partner(pend, args, kwargs=None):
-    """The other operand of ``add(a, b)`` / ``a.add_(b)`` when one operand is the pending BN-backward gradient
-    (plain sum, same shape and dtype); else None."""
-    if pend is None or len(args) != 2 or (kwargs and kwargs.get("alpha", 1) != 1):
-        return None
-    a, b = args
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
-        return None
-    o = b if _same(a, pend.out) else a if _same(b, pend.out) else None
-    if o is None or o.shape != pend.out.shape or o.dtype != pend.out.dtype:
-        return None
-    return o
-
-
-class _PendingThr:
-    """threshold_backward(grad, relu_out) not yet computed: its consumer (BN backward) masks on the fly."""
-    __slots__ = ("out", "grad", "relu_out", "thr")
-
-    def __init__(self, out, grad, relu_out, thr):
-        self.out, self.grad, self.relu_out, self.thr = out, grad, relu_out, thr
-
-    def materialize(self):
-        ew(self.out, [self.grad, self.relu_out], EW_THR_BWD, self.thr)
 
 
 @impl(aten.threshold_backward.default)
 def _thr_bwd(func, grad_output, self, threshold):
     out = _alloc_like_meta(func, (grad_output, self, threshold), {}, grad_output.device)
-    mode = NativeMode.current
+    mode = current_mode()
     if (mode is not None and mode.fuse and _cl_rows(grad_output) and _cl_rows(self) and _cl_rows(out)
             and grad_output.shape == self.shape):
-        mode._pend_thr = _PendingThr(out, grad_output, self, float(threshold))
+        mode.pend(_PendingThr(out, grad_output, self, float(threshold)))
         return out
     return ew(out, [grad_output, self], EW_THR_BWD, float(threshold))
 
@@ -552,20 +316,6 @@ def _zero_(func, self):
 
 
 # ---- concat / slicing -------------------------------------------------------------
-class _CatBuf:
-    """A reverse-filled concat buffer: NHWC [N, H, W, K], channels [front, K) live.  ``cat([y, x], 1)`` with x
-    the live tail writes y in front of it and returns the longer tail -- x is never copied again (DenseNet's
-    growing feature map, /root/reference/src/models/densenet.py:20-24: the reference copies the whole map per
-    layer)."""
-    __slots__ = ("buf", "front", "head")
-
-    def __init__(self, buf, front, head):
-        self.buf, self.front, self.head = buf, front, head
-
-    def tail(self):
-        return _nchw(self.buf[..., self.front:])
-
-
 def _cat_chain(mode, y: torch.Tensor, x: torch.Tensor):
     """``cat([y, x], 1)`` of 4-D activations through a concat buffer, or None (the plain copy path).
 
@@ -578,7 +328,7 @@ def _cat_chain(mode, y: torch.Tensor, x: torch.Tensor):
         return None
     N, Cy, H, W = y.shape
     Cx = x.shape[1]
-    ent = mode._catbufs.get(x.untyped_storage().data_ptr())
+    ent = mode._blk.catbufs.get(x.untyped_storage().data_ptr())
     if ent is not None and ent.front >= Cy and _same(x, ent.tail()):
         ew(_nchw(ent.buf[..., ent.front - Cy:ent.front]), [y], EW_COPY)
         ent.front -= Cy
@@ -586,7 +336,7 @@ def _cat_chain(mode, y: torch.Tensor, x: torch.Tensor):
         mode._cat_plan[ent.head] = max(mode._cat_plan.get(ent.head, 0), Cx + Cy)
         mode.fused["cat_in_place"] += 1
         return out
-    head = mode._cat_src.get((x.data_ptr(), tuple(x.shape)))
+    head = mode._blk.cat_src.get((x.data_ptr(), tuple(x.shape)))
     if head is not None:                 # learning: x is an earlier cat's output, the chain grows
         mode._cat_plan[head] = max(mode._cat_plan.get(head, 0), Cx + Cy)
         return None
@@ -599,14 +349,14 @@ def _cat_chain(mode, y: torch.Tensor, x: torch.Tensor):
     ew(ent.tail(), [x], EW_COPY)
     ew(_nchw(buf[..., ent.front - Cy:ent.front]), [y], EW_COPY)
     ent.front -= Cy
-    mode._catbufs[buf.untyped_storage().data_ptr()] = ent
+    mode._blk.catbufs[buf.untyped_storage().data_ptr()] = ent
     return ent.tail()
 
 
 @impl(aten.cat.default)
 def _cat(func, tensors, dim=0):
     tensors = [t for t in tensors if t.numel() > 0 or t.dim() > 1]
-    mode = NativeMode.current
+    mode = current_mode()
     head = None
     if mode is not None and mode.fuse and len(tensors) == 2 and tensors[0].dim() == 4 and dim % 4 == 1:
         r = _cat_chain(mode, tensors[0], tensors[1])
@@ -627,43 +377,9 @@ def _cat(func, tensors, dim=0):
         off += t.shape[d] if t.dim() else 0
     if mode is not None and mode.fuse and len(tensors) == 2 and tensors[0].dim() == 4 and dim % 4 == 1:
         x = tensors[1]
-        src = mode._cat_src.get((x.data_ptr(), tuple(x.shape)))
-        mode._cat_src[(out.data_ptr(), tuple(out.shape))] = src if src is not None else head
+        src = mode._blk.cat_src.get((x.data_ptr(), tuple(x.shape)))
+        mode._blk.cat_src[(out.data_ptr(), tuple(out.shape))] = src if src is not None else head
     return out
-
-
-class _PendingSliceBwd:
-    """slice_backward not computed yet (zeros + the gradient in its slice): autograd's sum of two of them that
-    tile the sliced dim (DPN's dual path: y[:, :d] and y[:, d:]) becomes two copies into one tensor -- no zero
-    fills, no add pass; any other read materialises it."""
-    __slots__ = ("out", "grad", "dim", "start", "end", "done")
-
-    def __init__(self, out, grad, dim, start, end):
-        self.out, self.grad, self.dim, self.start, self.end = out, grad, dim, start, end
-        self.done = False
-
-    def materialize(self):
-        self.done = True
-        fill_(self.out, 0.0)
-        ew(self.out.narrow(self.dim, self.start, self.end - self.start), [self.grad], EW_COPY)
-
-
-def _sb_pair(mode, args, kwargs=None):
-    """The two pending slice_backwards an ``add(a, b)`` sums when their slices tile the dim exactly, else None."""
-    if mode is None or not mode._pend_sb or len(args) != 2 or (kwargs and kwargs.get("alpha", 1) != 1):
-        return None
-    a, b = args
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or not (a.is_cuda and b.is_cuda):
-        return None
-    pa = mode._pend_sb.get(a.untyped_storage().data_ptr())
-    pb = mode._pend_sb.get(b.untyped_storage().data_ptr())
-    if (pa is None or pb is None or pa is pb or pa.done or pb.done or not (_same(a, pa.out) and _same(b, pb.out))
-            or pa.dim != pb.dim):
-        return None
-    lo, hi = (pa, pb) if pa.start <= pb.start else (pb, pa)
-    if lo.start != 0 or lo.end != hi.start or hi.end != pa.out.shape[pa.dim]:
-        return None
-    return lo, hi
 
 
 @impl(aten.slice_backward.default)
@@ -676,11 +392,10 @@ def _slice_bwd(func, grad_output, input_sizes, dim, start, end, step):
     d = dim % out.dim()
     lo = max(0, min(start, out.shape[d])) if start is not None else 0
     hi = max(lo, min(end, out.shape[d])) if end is not None else out.shape[d]
-    mode = NativeMode.current
+    mode = current_mode()
     if mode is not None and mode.fuse and step == 1 and hi - lo == grad_output.shape[d]:
         pend = _PendingSliceBwd(out, grad_output, d, lo, hi)
-        mode._pend_sb[out.untyped_storage().data_ptr()] = pend
-        mode._defer(out, pend.materialize)
+        mode._defer(pend)
         return out
     fill_(out, 0.0)
     ew(aten.slice.Tensor(out, dim, start, end, step), [grad_output], EW_COPY)
@@ -697,10 +412,9 @@ def _sum_like(func, self, dim, keepdim, dtype, scale_by_count: bool):
     cnt = 1
     for d in dims:
         cnt *= self.shape[d]
-    mode = NativeMode.current
-    pend = mode._pend_mul if mode is not None else None
-    if pend is not None and _same(self, pend.out):
-        mode._pend_mul = None
+    mode = current_mode()
+    pend, _ = _take(_PendingMul)
+    if pend is not None:
         kept = [d for d in range(self.dim()) if d not in dims and self.shape[d] > 1]
         # per-(sample, channel) sums (SE gates): the generic reduction, which the unfused sum takes too
         if out.numel() and _rowmajor_out(out) and len(kept) >= 2:   # sum(a * b): one dot reduction, the product never stored
@@ -708,7 +422,7 @@ def _sum_like(func, self, dim, keepdim, dtype, scale_by_count: bool):
             rd = RD_DOT_R if pend.out.dtype == torch.bfloat16 else RD_DOT_SHIFT
             reduce_sum(pend.a, dims, None, rd, b=pend.b, out=out,
                        scale=1.0 / max(cnt, 1) if scale_by_count else 1.0)
-            mode._defer(pend.out, pend.materialize)
+            mode._defer(pend)
             mode.fused["mul+sum"] += 1
             return out
         pend.materialize()
@@ -743,83 +457,6 @@ def _sum_all(func, self, dtype=None):
 
 
 # ---- BatchNorm -------------------------------------------------------------------
-def _rows_ld(t: torch.Tensor) -> Optional[int]:
-    """Row stride (elements) when t is an [M, C] row matrix in memory -- channels-last 4-D or 2-D with unit-stride
-    channels, compact or a channel slice of a wider one (a concat buffer's tail, a padded conv output's first C
-    channels) -- with 16-B channel vectors (8-B for bf16 C % 8 != 0); else None."""
-    if t.dim() == 4:
-        ld = _row_stride(t.permute(0, 2, 3, 1))
-    elif t.dim() == 2 and t.stride(1) == 1:
-        ld = t.stride(0) if t.shape[0] > 1 else t.shape[1]
-    else:
-        return None
-    C = t.shape[1]
-    if ld is None or C % 4 or ld < C or t.dtype not in (torch.float32, torch.bfloat16) or t.numel() == 0:
-        return None
-    align = 16 if (t.dtype == torch.float32 or C % 8 == 0) else 8
-    if t.data_ptr() % align or (ld * t.element_size()) % align:
-        return None
-    return int(ld)
-
-
-def _cl_rows(t: torch.Tensor) -> bool:
-    return _rows_ld(t) is not None
-
-
-def _same_geom(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return a.shape == b.shape and a.stride() == b.stride()
-
-
-def _same(a, b) -> bool:
-    return isinstance(a, torch.Tensor) and a.data_ptr() == b.data_ptr() and _same_geom(a, b) and a.dtype == b.dtype
-
-
-class _PendingBN:
-    """A BatchNorm output whose apply pass (x * scale + shift [+ res]) has not run yet: if the next op is
-    a residual add of it (identity or projection shortcut), the add joins the pending pass; if the next
-    op is its ReLU, everything becomes one pass (EW_FMA_RELU / EW_FMA_ADD_RELU); any other op
-    materialises it first."""
-    __slots__ = ("out", "x", "scale", "shift", "res")
-
-    def __init__(self, out, x, scale, shift, res=None):
-        self.out, self.x, self.scale, self.shift, self.res = out, x, scale, shift, res
-
-    def inputs(self):
-        return [self.x, self.scale, self.shift] + ([] if self.res is None else [self.res])
-
-    def rounding(self) -> float:
-        # the unfused BN stores its output before the add reads it: round there too (bit-identical results)
-        return 1.0 if self.res is not None and self.out.dtype == torch.bfloat16 else 0.0
-
-    def materialize(self):
-        ew(self.out, self.inputs(), EW_FMA if self.res is None else EW_FMA_ADD, 0.0, self.rounding())
-
-    def relu(self, out):
-        return ew(out, self.inputs(), EW_FMA_RELU if self.res is None else EW_FMA_ADD_RELU, 0.0, self.rounding())
-
-
-def _bn_add_partner(pend, args, kwargs=None):
-    """The other operand of ``add.Tensor(a, b)`` when one operand is the pending BN output and the pair can
-    join the pending pass (no alpha, same geometry and dtype, no residual taken yet); else None."""
-    if pend is None or pend.res is not None or len(args) < 2 or len(args) > 2 or (kwargs and kwargs.get("alpha", 1) != 1):
-        return None
-    a, b = args[0], args[1]
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
-        return None
-    o = b if _same(a, pend.out) else a if _same(b, pend.out) else None
-    if o is None or o is pend.out or o.dtype != pend.out.dtype or not _same_geom(o, pend.out):
-        return None
-    return o
-
-
-def _mode_pending_bn(t):
-    mode = NativeMode.current
-    if mode is None or mode._pend_bn is None or not _same(t, mode._pend_bn.out):
-        return None
-    pend, mode._pend_bn = mode._pend_bn, None
-    return pend
-
-
 @impl(aten.native_batch_norm.default)
 def _bn(func, input, weight, bias, running_mean, running_var, training, momentum, eps):
     x = input
@@ -829,22 +466,22 @@ def _bn(func, input, weight, bias, running_mean, running_var, training, momentum
     f32 = dict(dtype=torch.float32, device=dev)
     scale, shift_out = torch.empty(C, **f32), torch.empty(C, **f32)
     nat = _nat()
-    mode = NativeMode.current
+    mode = current_mode()
     ldx = _rows_ld(x)
     rows = ldx is not None
-    if mode is not None and not (training and rows):
-        mode._flush_ctr()
+    ctr, _ = _take(_PendingCtr)
+    if ctr is not None and not (training and rows):
+        ctr.materialize()           # only the rows kernel bumps the counter itself
+        ctr = None
     if training and rows:
         # channels-last rows: moments (slab partials) + ONE finalize that also derives the coefficients and
         # the running stats (2 launches; the generic path below takes 4)
         save_mean, save_invstd = torch.empty(C, **f32), torch.empty(C, **f32)
-        p = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
         part = torch.empty(int(nat.z_reduce_rows_ws_floats(M, C)), **f32)
-        ctr = mode._take_ctr() if mode is not None else None
-        nat.z_bn_rows_fwd(_st(dev), x.data_ptr(), _DT[x.dtype], ldx, p(running_mean), C, M, part.data_ptr(), part.numel(),
-                          p(weight), p(bias), p(running_mean), p(running_var), float(eps),
+        nat.z_bn_rows_fwd(_st(dev), x.data_ptr(), _DT[x.dtype], ldx, _ptr(running_mean), C, M, part.data_ptr(),
+                          part.numel(), _ptr(weight), _ptr(bias), _ptr(running_mean), _ptr(running_var), float(eps),
                           float(momentum if momentum is not None else 0.1), save_mean.data_ptr(), save_invstd.data_ptr(),
-                          scale.data_ptr(), shift_out.data_ptr(), p(ctr))
+                          scale.data_ptr(), shift_out.data_ptr(), _ptr(ctr.t if ctr else None))
     elif training:
         acc = torch.empty(2 * C, **f32)
         fill_(acc, 0.0)
@@ -852,20 +489,19 @@ def _bn(func, input, weight, bias, running_mean, running_var, training, momentum
         # moments of (x - running_mean): no catastrophic cancellation in E[d^2] - E[d]^2
         reduce_sum(x, dims, acc[:C], RD_SUMSQ_SHIFT, shift=running_mean, acc2=acc[C:])
         save_mean, save_invstd = torch.empty(C, **f32), torch.empty(C, **f32)
-        p = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
-        nat.z_bn_fwd_coeffs(_st(dev), acc.data_ptr(), acc[C:].data_ptr(), p(running_mean), C, M, p(weight), p(bias),
-                            p(running_mean), p(running_var), float(eps), float(momentum if momentum is not None else 0.1),
-                            1, save_mean.data_ptr(), save_invstd.data_ptr(), scale.data_ptr(), shift_out.data_ptr())
+        nat.z_bn_fwd_coeffs(_st(dev), acc.data_ptr(), acc[C:].data_ptr(), _ptr(running_mean), C, M, _ptr(weight),
+                            _ptr(bias), _ptr(running_mean), _ptr(running_var), float(eps),
+                            float(momentum if momentum is not None else 0.1), 1, save_mean.data_ptr(),
+                            save_invstd.data_ptr(), scale.data_ptr(), shift_out.data_ptr())
     else:
-        p = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
-        nat.z_bn_fwd_coeffs(_st(dev), 0, 0, 0, C, M, p(weight), p(bias), p(running_mean), p(running_var), float(eps),
-                            0.0, 0, 0, 0, scale.data_ptr(), shift_out.data_ptr())
+        nat.z_bn_fwd_coeffs(_st(dev), 0, 0, 0, C, M, _ptr(weight), _ptr(bias), _ptr(running_mean), _ptr(running_var),
+                            float(eps), 0.0, 0, 0, 0, scale.data_ptr(), shift_out.data_ptr())
         save_mean = torch.empty(0, **f32)
         save_invstd = torch.empty(0, **f32)
     bshape = [1, C] + [1] * (x.dim() - 2)
     out = torch.empty_like(x)      # channels-last compact even for a row-strided x (empty_like of a non-dense view)
     if mode is not None and mode.fuse and rows and _cl_rows(out):
-        mode._pend_bn = _PendingBN(out, x, scale.view(bshape), shift_out.view(bshape))
+        mode.pend(_PendingBN(out, x, scale.view(bshape), shift_out.view(bshape)))
     else:
         ew(out, [x, scale.view(bshape), shift_out.view(bshape)], EW_FMA)
     return out, save_mean, save_invstd
@@ -899,12 +535,10 @@ def _bn_bwd(func, grad_out, input, weight, running_mean, running_var, save_mean,
     gw = gw if gw is not None else (torch.empty(C, **f32) if output_mask[1] else None)
     gb = (_param_grad(weight, bias=True) if output_mask[2] else None) if weight is not None else None
     gb = gb if gb is not None and gb.shape[0] == C else (torch.empty(C, **f32) if output_mask[2] else None)
-    p = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
-    mode = NativeMode.current
-    thr = None
-    if mode is not None and mode._pend_thr is not None and _same(g, mode._pend_thr.out):
-        thr, mode._pend_thr = mode._pend_thr, None   # this BN's ReLU backward, fused into its sums and apply
-        mode._defer(thr.out, thr.materialize)
+    mode = current_mode()
+    thr, _ = _take(_PendingThr)
+    if thr is not None:             # this BN's ReLU backward, fused into its sums and apply
+        mode._defer(thr)
         mode.fused["relu_bwd+bn_bwd"] += 1
         g = thr.grad
     ldg, ldx = _rows_ld(g), _rows_ld(x)
@@ -914,8 +548,8 @@ def _bn_bwd(func, grad_out, input, weight, running_mean, running_var, save_mean,
         part = torch.empty(int(nat.z_reduce_rows_ws_floats(M, C)), **f32)
         nat.z_bn_rows_bwd(_st(dev), g.data_ptr(), _DT[g.dtype], ldg, x.data_ptr(), _DT[x.dtype], ldx,
                           thr.relu_out.data_ptr() if thr else 0, _DT[thr.relu_out.dtype] if thr else 0, ldf,
-                          thr.thr if thr else 0.0, save_mean.data_ptr(), save_invstd.data_ptr(), p(weight), C, M,
-                          part.data_ptr(), part.numel(), k.data_ptr(), bb.data_ptr(), cc.data_ptr(), p(gw), p(gb))
+                          thr.thr if thr else 0.0, save_mean.data_ptr(), save_invstd.data_ptr(), _ptr(weight), C, M,
+                          part.data_ptr(), part.numel(), k.data_ptr(), bb.data_ptr(), cc.data_ptr(), _ptr(gw), _ptr(gb))
     else:
         if thr is not None:
             thr.materialize()
@@ -925,8 +559,8 @@ def _bn_bwd(func, grad_out, input, weight, running_mean, running_var, save_mean,
         dims = [0] + list(range(2, x.dim()))
         reduce_sum(g, dims, acc[:C], RD_DOT_SHIFT, b=x, shift=save_mean, acc2=acc[C:])
         _nat().z_bn_bwd_coeffs(_st(dev), acc.data_ptr(), acc[C:].data_ptr(), save_mean.data_ptr(),
-                               save_invstd.data_ptr(), p(weight), C, M, k.data_ptr(), bb.data_ptr(), cc.data_ptr(),
-                               p(gw), p(gb))
+                               save_invstd.data_ptr(), _ptr(weight), C, M, k.data_ptr(), bb.data_ptr(), cc.data_ptr(),
+                               _ptr(gw), _ptr(gb))
     gi = None
     if output_mask[0]:
         bshape = [1, C] + [1] * (x.dim() - 2)
@@ -934,7 +568,7 @@ def _bn_bwd(func, grad_out, input, weight, running_mean, running_var, save_mean,
         ins = [g, k.view(bshape), x, bb.view(bshape), cc.view(bshape)] + ([thr.relu_out] if thr is not None else [])
         pend = _PendingBNB(gi, ins, thr.thr if thr is not None else 0.0)
         if mode is not None and mode.fuse:
-            mode._pend_bnb = pend            # autograd's accumulation add of this gradient may join the pass
+            mode.pend(pend)                  # autograd's accumulation add of this gradient may join the pass
         else:
             pend.materialize()
     if gw is not None and weight is not None and gw.dtype != weight.dtype:
@@ -1063,7 +697,7 @@ def _nll_bwd(func, grad_output, self, target, weight, reduction, ignore_index, t
 # ---- RNG (dropout / drop-connect) -----------------------------------------------------
 @impl(aten.bernoulli_.float)
 def _bernoulli_(func, self, p=0.5, generator=None):
-    mode = NativeMode.current
+    mode = current_mode()
     ew(self, [], EW_BERN, float(p), seed=mode.seed, ctr=mode.rng_ctr(self.device))
     _nat().z_ctr_bump(_st(self.device), mode.rng_ctr(self.device).data_ptr())
     return self
@@ -1122,24 +756,6 @@ def _conv_kind(C, O, groups, k, stride, pad, dil):
     return "gconv"
 
 
-def _row_stride(t: torch.Tensor) -> Optional[int]:
-    """Row stride (elements) when ``t`` [..., C] is evenly spaced rows of unit-stride channels (a compact tensor
-    or a channel slice of one), else None."""
-    if t.dim() < 2 or t.stride(-1) != 1:
-        return None
-    ld = expect = None
-    for d in range(t.dim() - 2, -1, -1):
-        if t.shape[d] == 1:
-            continue
-        if ld is None:
-            ld, expect = t.stride(d), t.stride(d) * t.shape[d]
-        elif t.stride(d) != expect:
-            return None
-        else:
-            expect *= t.shape[d]
-    return int(ld) if ld is not None else int(t.shape[-1])
-
-
 def _pad_c(t: torch.Tensor, c8: int, cache: bool = False) -> torch.Tensor:
     """NHWC bf16 [.., C] (possibly a channel slice) -> contiguous [.., c8], zero channels C..c8.  ``cache``:
     reuse / keep the padded copy for the rest of the NativeMode block (a conv's input is padded by its
@@ -1147,10 +763,10 @@ def _pad_c(t: torch.Tensor, c8: int, cache: bool = False) -> torch.Tensor:
     C = t.shape[-1]
     if C == c8 and t.is_contiguous():
         return t
-    mode = NativeMode.current
+    mode = current_mode()
     key = ("pad", t.data_ptr(), tuple(t.shape), tuple(t.stride()), c8)
-    if cache and mode is not None and key in mode._wcache:
-        return mode._wcache[key][1]
+    if cache and mode is not None and key in mode._blk.wcache:
+        return mode._blk.wcache[key][1]
     out = torch.empty(*t.shape[:-1], c8, dtype=torch.bfloat16, device=t.device)
     rows = t.numel() // C if C else 0
     if t.dtype == torch.bfloat16 and rows and _row_stride(t) is not None:
@@ -1160,7 +776,7 @@ def _pad_c(t: torch.Tensor, c8: int, cache: bool = False) -> torch.Tensor:
             fill_(out[..., C:], 0.0)
         ew(out[..., :C], [t], EW_COPY)
     if cache and mode is not None:
-        mode._wcache[key] = (t, out)
+        mode._blk.wcache[key] = (t, out)
     return out
 
 
@@ -1191,15 +807,15 @@ def _packed(w32, O8: int, C8: int, st: int, pd: int, need_wd: bool = False, grou
     the SGD, outside the block).  Weights living in the trainer's flat parameter storage
     (:attr:`NativeMode.stable_storage`) are remembered: the next block packs all of them in one multi-tensor
     launch at its first conv (and all DGRAD images at its first conv backward) instead of one launch each."""
-    mode = NativeMode.current
-    cache = mode._wcache if mode is not None else None
+    mode = current_mode()
+    cache = mode._blk.wcache if mode is not None else None
     key = (w32.data_ptr(), tuple(w32.shape), tuple(w32.stride()), O8, C8, st, pd, groups)
     if mode is not None:
-        if not mode._prepacked:
-            mode._prepacked = True
+        if not mode._blk.prepacked:
+            mode._blk.prepacked = True
             mode._prepack(wd=False)
-        if need_wd and not mode._prepacked_wd:
-            mode._prepacked_wd = True
+        if need_wd and not mode._blk.prepacked_wd:
+            mode._blk.prepacked_wd = True
             mode._prepack(wd=True)
         if mode.stable_storage and w32.untyped_storage().data_ptr() == mode.stable_storage:
             mode._pack_plan.setdefault(key, w32)
@@ -1270,24 +886,24 @@ def _wred_part(out: Optional[torch.Tensor], floats: int):
     ONE wgrad_reduce_multi launch (per 32) sums them all when anything reads a pending slot, or at the mode's flush
     (bit-identical to the per-conv reduce: conv_igemm.hip wgrad_reduce.h; ~120 launches per DenseNet step).
     (None, None): reduce right away in the shared workspace."""
-    mode = NativeMode.current
+    mode = current_mode()
     if mode is None or not mode.defer_wred or out is None or floats <= 0:
         return None, None
     part = torch.empty(floats, dtype=torch.float32, device=out.device)
-    mode._wred_keep.append(part)
-    mode._wred_ptrs.add(out.data_ptr())
-    return part, mode._wred
+    mode._blk.wred_keep.append(part)
+    mode._blk.wred_ptrs.add(out.data_ptr())
+    return part, mode._blk.wred
 
 
 def _dw_padded_weight(w32: torch.Tensor, C8: int) -> torch.Tensor:
     """fp32 [C8, 1, R, R] depthwise weights with zero channels C..C8, made once per NativeMode block."""
-    mode = NativeMode.current
+    mode = current_mode()
     key = ("dwpad", w32.data_ptr(), tuple(w32.shape), C8)
-    if mode is not None and key in mode._wcache:
-        return mode._wcache[key][1]
+    if mode is not None and key in mode._blk.wcache:
+        return mode._blk.wcache[key][1]
     wp = _pad_o(w32.contiguous(), C8)
     if mode is not None:
-        mode._wcache[key] = (w32, wp)
+        mode._blk.wcache[key] = (w32, wp)
     return wp
 
 
@@ -1309,7 +925,7 @@ def _param_grad(w: Optional[torch.Tensor], bias: bool = False) -> Optional[torch
     writes the parameter gradient straight into it and autograd's AccumulateGrad adopts the tensor as ``p.grad``
     (the trainer clears ``p.grad`` before backward, :meth:`fedmi.engine.torch_engine.TorchTrainer._step_body`):
     no accumulation pass per parameter (~360 launches per DenseNet step).  None: allocate as usual."""
-    mode = NativeMode.current
+    mode = current_mode()
     if (mode is None or mode.grad_flat is None or not isinstance(w, torch.Tensor) or not w.is_cuda
             or w.dtype != torch.float32 or not w.is_contiguous() or w.untyped_storage().data_ptr() != mode.stable_storage):
         return None
@@ -1320,9 +936,9 @@ def _param_grad(w: Optional[torch.Tensor], bias: bool = False) -> Optional[torch
             return None
         off, n = ent
         shape = (n,)
-    if off + n > mode.grad_flat.numel() or off in mode._grad_taken:
+    if off + n > mode.grad_flat.numel() or off in mode._blk.grad_taken:
         return None
-    mode._grad_taken.add(off)
+    mode._blk.grad_taken.add(off)
     return mode.grad_flat[off:off + n].view(shape)
 
 
@@ -1469,7 +1085,6 @@ _PASSTHROUGH = _ops(
 )
 
 
-_BN_FWD = _ops("native_batch_norm", "miopen_batch_norm")
 # in-place ops among the native impls (their first argument is written)
 _INPLACE = _ops("add_.Tensor", "sub_.Tensor", "mul_.Tensor", "div_.Scalar", "relu_", "copy_", "fill_.Scalar",
                 "zero_", "bernoulli_.float")
@@ -1496,10 +1111,23 @@ class _MixedDtypeConv(TorchFunctionMode):
         return func(*args, **kwargs)
 
 
+class _Block:
+    """What lives for one ``with`` block of a :class:`NativeMode`: made by ``__enter__``, dropped by ``__exit__``."""
+
+    def __init__(self):
+        self.wcache = {}                # packed conv weights / padded inputs (see _packed, _pad_c)
+        self.prepacked = self.prepacked_wd = False
+        self.catbufs, self.cat_src = {}, {}   # storage ptr -> _CatBuf; (ptr, shape) of a plain cat output -> head
+        self.grad_taken = set()         # flat-gradient slots handed out (see _param_grad)
+        self.pending = []               # results whose pass waits for the next op (see zoo_fusion)
+        self.claimed = []               # (result, join answer): what the running op will consume
+        self.pair = None                # the two deferred slice gradients the running add sums (see _sb_pair)
+        self.dead = {}                  # storage ptr -> result with materialize(): a tensor nobody wrote yet
+        self.wred, self.wred_keep, self.wred_ptrs = [], [], set()   # deferred WGRAD reductions (see _wred_part)
+
+
 class NativeMode(TorchDispatchMode):
     """Route a training step's aten ops to fedmi's HIP kernels (see module docstring)."""
-
-    current: "NativeMode" = None
 
     def __init__(self, strict: bool = False, seed: int = 0, fuse: bool = True, discard_unread: bool = False):
         super().__init__()
@@ -1513,35 +1141,39 @@ class NativeMode(TorchDispatchMode):
         self.fallbacks = collections.Counter()
         self.native_ops = collections.Counter()
         self._ctr = {}
-        self.fuse = bool(fuse)          # BN -> ReLU (forward) and ReLU-backward -> BN-backward fusion
-        self._pend_bn: Optional[_PendingBN] = None
-        self._pend_thr: Optional[_PendingThr] = None
-        self._dead = {}                 # storage ptr -> materialiser of a tensor a fused op never wrote
+        self.fuse = bool(fuse)          # the peephole fusions of zoo_fusion (off: every op runs its own pass)
+        self._blk: Optional[_Block] = None   # the running block's state
         self.fused = collections.Counter()
         self.packs = collections.Counter()   # weight images packed by the batched per-block launches
         self.scalar_ew = collections.Counter()   # (op, shape, strides) of elementwise passes on the scalar kernel
         self.ew_ops = collections.Counter()      # (aten op, elementwise op code) -> passes
         self.diag = False                        # collect scalar_ew / ew_ops (tools/prof_native_mode.py)
-        self._wcache = {}               # packed conv weights of the current block (see _packed)
-        self._pend_ctr: Optional[torch.Tensor] = None   # a BN counter increment waiting for its BN forward
-        self._pend_bnb: Optional[_PendingBNB] = None    # a BN input gradient waiting for its accumulation add
-        self._pend_mul: Optional[_PendingMul] = None    # a product waiting for the reduction that sums it
-        self._pend_sb = {}              # storage ptr -> _PendingSliceBwd (deferred; see _sb_pair)
         self.stable_storage = 0         # data_ptr of the trainer's flat parameter storage (set by the trainer)
         self._pack_plan, self._wd_plan = {}, {}   # weight-image keys of stable weights -> fp32 master (kept)
         self.grad_flat: Optional[torch.Tensor] = None   # the trainer's flat gradient buffer (see _param_grad)
         self.bias_of = {}               # weight storage offset -> (bias offset, numel) of the same module
-        self._grad_taken = set()
-        self._prepacked = self._prepacked_wd = False
         self._cat_plan = {}             # concat-chain head shapes -> final width (kept across blocks)
-        self._catbufs = {}              # storage ptr -> _CatBuf of the current block
-        self._cat_src = {}              # (ptr, shape) of a plain cat output of this block -> its chain head
         # deferred WGRAD reductions (see _wred_part): FEDMI_WRED_DEFER=0 reduces each right away (A/B)
         self.defer_wred = os.environ.get("FEDMI_WRED_DEFER", "1") != "0"
-        self._wred, self._wred_keep, self._wred_ptrs = [], [], set()
 
-    def _defer(self, t: torch.Tensor, materialize) -> None:
-        self._dead[t.untyped_storage().data_ptr()] = materialize
+    def pend(self, result) -> None:
+        """A producer impl leaves ``result`` unwritten: the next op consumes it or has it materialised."""
+        self._blk.pending.append(result)
+
+    def take(self, cls):
+        """(result, join answer) of kind ``cls`` that the running op claimed for its impl, or (None, None)."""
+        for i, (p, _) in enumerate(self._blk.claimed):
+            if type(p) is cls:
+                return self._blk.claimed.pop(i)
+        return None, None
+
+    def take_pair(self):
+        pair, self._blk.pair = self._blk.pair, None
+        return pair
+
+    def _defer(self, result) -> None:
+        """``result.out`` stays unwritten until something reads it (see :meth:`_read`)."""
+        self._blk.dead[result.out.untyped_storage().data_ptr()] = result
 
     def _prepack(self, wd: bool) -> None:
         """Pack every remembered weight image (``wd``: DGRAD images) of the trainer's parameters in as few
@@ -1550,7 +1182,7 @@ class NativeMode(TorchDispatchMode):
         items = []
         for key, w32 in plan.items():
             O8, C8, st, pd, groups = key[3:]
-            ent = self._wcache.setdefault(key, (w32, {}))[1]
+            ent = self._blk.wcache.setdefault(key, (w32, {}))[1]
             if wd:
                 if "wd" not in ent and w32.shape[0] == O8 and w32.is_contiguous() and groups == 1:
                     ent["wd"] = _wd_image(w32, O8, C8, st, pd)
@@ -1563,85 +1195,67 @@ class NativeMode(TorchDispatchMode):
             (CV.dgrad_pack_weights if wd else CV.pack_weights)(items)
             self.packs["wd" if wd else "wp"] += len(items)
 
-    def _flush_ctr(self) -> None:
-        if self._pend_ctr is not None:
-            t, self._pend_ctr = self._pend_ctr, None
-            ew(t, [t], EW_ADDS, 1.0)
-
-    def _take_ctr(self) -> Optional[torch.Tensor]:
-        t, self._pend_ctr = self._pend_ctr, None
-        return t
-
     def _flush_wred(self) -> None:
-        if self._wred:
-            items, self._wred = self._wred, []
-            CV.wgrad_reduce_multi(items, self._wred_keep[0].device)
-        self._wred_keep, self._wred_ptrs = [], set()
+        blk = self._blk
+        if blk.wred:
+            items, blk.wred = blk.wred, []
+            CV.wgrad_reduce_multi(items, blk.wred_keep[0].device)
+        blk.wred_keep, blk.wred_ptrs = [], set()
+
+    @staticmethod
+    def _materialize(results) -> None:
+        for r in sorted(results, key=lambda r: r.order):
+            r.materialize()
 
     def _flush(self) -> None:
+        """Everything pending is written: a block ends, or the host reads device data."""
+        blk = self._blk
         self._flush_wred()
-        self._flush_ctr()
-        if self._pend_mul is not None:
-            pend, self._pend_mul = self._pend_mul, None
-            pend.materialize()
-        if self._pend_bnb is not None:
-            pend, self._pend_bnb = self._pend_bnb, None
-            pend.materialize()
-        if self._pend_bn is not None:
-            pend, self._pend_bn = self._pend_bn, None
-            pend.materialize()
-        if self._pend_thr is not None:
-            pend, self._pend_thr = self._pend_thr, None
-            pend.materialize()
+        left, blk.pending, blk.claimed = [r for r, _ in blk.claimed] + blk.pending, [], []
+        self._materialize(left)
 
-    def _touch(self, args, kwargs) -> None:
-        """Before an op runs: materialise a pending result it does not fuse with, and any deferred tensor
-        it reads (a fused op left it unwritten)."""
-        if self._pend_ctr is not None and self._func not in _BN_FWD:
-            self._flush_ctr()
-        if self._pend_mul is not None and not (self._func in (aten.sum.dim_IntList, aten.mean.dim) and args
-                                               and _same(args[0], self._pend_mul.out)):
-            pend, self._pend_mul = self._pend_mul, None
-            pend.materialize()
-        if self._pend_bnb is not None and not (self._func in (aten.add.Tensor, aten.add_.Tensor)
-                                               and _bnb_add_partner(self._pend_bnb, args, kwargs) is not None):
-            pend, self._pend_bnb = self._pend_bnb, None
-            pend.materialize()
-        if self._pend_bn is not None and not self._fuses_bn(args, kwargs):
-            pend, self._pend_bn = self._pend_bn, None
-            pend.materialize()
-        if self._pend_thr is not None and not self._fuses_thr(args):
-            pend, self._pend_thr = self._pend_thr, None
-            pend.materialize()
-        if self._wred_ptrs and any(t.data_ptr() in self._wred_ptrs for t in _iter_tensors(args, kwargs)):
+    def _touch(self, func, args, kwargs) -> None:
+        """Before an op runs: every pending result is asked ONCE whether the op consumes it -- then it is claimed
+        for the op's impl together with its answer (:meth:`take`) -- and materialised otherwise; then whatever
+        the op reads is written."""
+        blk = self._blk
+        waiting, blk.pending = blk.pending, []
+        for r in sorted(waiting, key=lambda r: r.order):
+            answer = r.joins(func, args, kwargs)
+            if answer is None:
+                r.materialize()
+            else:
+                blk.claimed.append((r, answer))
+        if blk.wred_ptrs and any(t.data_ptr() in blk.wred_ptrs for t in _iter_tensors(args, kwargs)):
             self._flush_wred()              # an op reads a weight gradient whose reduction is still pending
-        if self._dead and self._pend_sb and self._func is aten.add.Tensor and _sb_pair(self, args, kwargs):
-            return                          # the add reads both pending slice gradients' sources itself
-        if self._dead:
+        blk.pair = _sb_pair(blk.dead, args, kwargs) if func is aten.add.Tensor else None
+        if blk.pair is None:                # (else the add reads both deferred slice gradients' sources itself)
+            self._read(args, kwargs)
+
+    def _read(self, args, kwargs) -> None:
+        """Materialise every deferred tensor among the operands (a fused op left it unwritten)."""
+        dead = self._blk.dead
+        if dead:
             for t in _iter_tensors(args, kwargs):
-                fn = self._dead.pop(t.untyped_storage().data_ptr(), None) if t.is_cuda else None
-                if fn is not None:
-                    fn()
+                r = dead.pop(t.untyped_storage().data_ptr(), None)
+                if r is not None:
+                    r.materialize()
+
+    def _settle(self, args, kwargs) -> None:
+        """After an op's impl, and so before ATen runs an op no impl took: what the op claimed and did not
+        take is written -- nothing reads a tensor that is still pending."""
+        blk = self._blk
+        if blk.claimed:
+            left, blk.claimed = [r for r, _ in blk.claimed], []
+            self._materialize(left)
+        if blk.pair is not None:
+            blk.pair = None
+            self._read(args, kwargs)
 
     _func = None
 
     def _func_name(self) -> str:
         return str(self._func).replace("aten.", "") if self._func is not None else "?"
-
-    def _fuses_bn(self, args, kwargs=None) -> bool:
-        if self._func is aten.add.Tensor:
-            return _bn_add_partner(self._pend_bn, args, kwargs) is not None
-        return (self._func in (aten.relu.default, aten.relu_.default) and len(args) > 0
-                and _same(args[0], self._pend_bn.out))
-
-    def _fuses_thr(self, args) -> bool:
-        if self._func is aten.native_batch_norm_backward.default:
-            g = args[0] if args else None
-        elif self._func is aten.miopen_batch_norm_backward.default:
-            g = args[1] if len(args) > 1 else None
-        else:
-            return False
-        return _same(g, self._pend_thr.out)
 
     def rng_ctr(self, dev) -> torch.Tensor:
         dev = torch.device(dev)
@@ -1650,13 +1264,8 @@ class NativeMode(TorchDispatchMode):
         return self._ctr[dev]
 
     def __enter__(self):
-        self._prev = NativeMode.current
-        NativeMode.current = self
-        self._wcache = {}
-        self._pend_sb = {}
-        self._prepacked = self._prepacked_wd = False
-        self._catbufs, self._cat_src = {}, {}
-        self._grad_taken = set()
+        self._prev = set_current_mode(self)
+        self._blk = _Block()
         self._fn_mode = _MixedDtypeConv()
         self._fn_mode.__enter__()
         return super().__enter__()
@@ -1665,14 +1274,11 @@ class NativeMode(TorchDispatchMode):
         try:
             self._flush()
             if not self.discard_unread and exc[0] is None:
-                for fn in list(self._dead.values()):
-                    fn()
+                for r in list(self._blk.dead.values()):
+                    r.materialize()
         finally:
-            self._dead.clear()
-            self._pend_sb = {}
-            self._wcache = {}
-            self._catbufs, self._cat_src = {}, {}
-        NativeMode.current = self._prev
+            self._blk = None
+        set_current_mode(self._prev)
         try:
             return super().__exit__(*exc)
         finally:
@@ -1683,24 +1289,23 @@ class NativeMode(TorchDispatchMode):
         if func in _PASSTHROUGH:
             if func is aten._local_scalar_dense.default:     # reads device data: everything must be written
                 self._flush()
-                self._touch(args, kwargs)
+                self._read(args, kwargs)
             return func(*args, **kwargs)
         self._func = func
-        if self._catbufs and func in _INPLACE and isinstance(args[0], torch.Tensor) and args[0].is_cuda \
-                and args[0].untyped_storage().data_ptr() in self._catbufs:
+        catbufs = self._blk.catbufs
+        if catbufs and func in _INPLACE and isinstance(args[0], torch.Tensor) and args[0].is_cuda \
+                and args[0].untyped_storage().data_ptr() in catbufs:
             raise RuntimeError(f"native_mode: {func} writes in place into a shared concat buffer (a cat output "
                                "aliases the inputs of later cats); run this model with NativeMode(fuse=False)")
-        self._touch(args, kwargs)
+        self._touch(func, args, kwargs)
         fn = _IMPL.get(func)
         on_gpu = _dev(args, tuple(kwargs.values())) is not None
-        if fn is not None and on_gpu:
-            out = fn(func, *args, **kwargs)
-            if out is ATEN:
-                return func(*args, **kwargs)
-            if out is not None:
-                self.native_ops[str(func)] += 1
-                return out
-        if on_gpu:
+        out = fn(func, *args, **kwargs) if fn is not None and on_gpu else None
+        self._settle(args, kwargs)
+        if out is not None and out is not ATEN:
+            self.native_ops[str(func)] += 1
+            return out
+        if on_gpu and out is not ATEN:      # (ATEN: the op is legitimately ATen's, not a fallback)
             if self.strict:
                 raise RuntimeError(f"native_mode: no native kernel for {func}")
             if not self.fallbacks[str(func)]:   # never silent: once per op, counted in .fallbacks (bench JSON)

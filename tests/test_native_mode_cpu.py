@@ -7,6 +7,7 @@ op set against NativeMode's tables.  The numerics of those implementations are G
 (tests/test_native_mode_gpu.py).
 """
 import collections
+import re
 
 import pytest
 import torch
@@ -15,6 +16,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 from fedmi.models import build_model
 from fedmi.ops import native_mode as nm
+from fedmi.ops import zoo_launch as zl
 
 # one (small) member per family; the GPU tests train them under the native mode
 HYBRID_MODELS = ["densenet_cifar", "DenseNet121", "ResNeXt29_2x64d", "ResNeXt29_32x4d", "DPN26", "ShuffleNetG2",
@@ -62,10 +64,27 @@ def test_every_step_op_is_native(name):
 def test_tables_disjoint_and_named():
     assert not (set(nm._IMPL) & nm._PASSTHROUGH)
     assert len(nm._IMPL) >= 40
-    # every elementwise op code the Python side uses exists in the kernel's enum
+    # the op / dtype codes are written twice, in the kernels' enums and in Python: the two sides agree, entry by entry
     src = open(nm.__file__.replace("fedmi/ops/native_mode.py", "csrc/kernels/zoo_ops.hip")).read()
+
+    def enum(name):
+        body = re.search(r"enum\s+%s\s*:\s*int\s*\{(.*?)\}" % name, src, re.S).group(1)
+        body = re.sub(r"//[^\n]*", "", body)
+        return {k: int(v) for k, v in re.findall(r"(\w+)\s*=\s*(\d+)", body)}
+
+    ew, rd, zdt = enum("EwOp"), enum("RdOp"), enum("ZDtype")
+    assert len(ew) == 21 and len(rd) == 4 and len(zdt) == 3
     for code in ("EW_COPY", "EW_ADD", "EW_MULS", "EW_BNB", "EW_BERN", "EW_ADDS", "EW_DIV"):
-        assert code in src
+        assert code in ew
+    for codes, prefix in ((ew, "EW_"), (rd, "RD_")):
+        py = {k: v for k, v in vars(zl).items() if k.startswith(prefix)}
+        assert py == codes, (sorted(set(py) ^ set(codes)), {k: (py[k], codes[k]) for k in set(py) & set(codes)
+                                                            if py[k] != codes[k]})
+        for k, v in codes.items():          # native_mode re-exports what it imports: the same values
+            assert getattr(nm, k) == v
+    assert {("Z_" + {torch.float32: "F32", torch.bfloat16: "BF16", torch.int64: "I64"}[t]): c
+            for t, c in zl._DT.items()} == zdt
+    assert nm._DT is zl._DT
 
 
 def test_conv_kind_routing():
