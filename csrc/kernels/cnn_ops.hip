@@ -94,8 +94,7 @@ struct BNArgs {
 // per-channel scale/shift of channels [c_lo, c_lo + CC) into LDS sc[0..CC), sh[0..CC); the
 // commit block (its row chunk 0) also commits the running stats of those channels
 FEDMI_DEV void bn_coeffs(const BNArgs& a, int C, int M, float eps, float mom, int train, float* sc, float* sh,
-                         int c_lo = 0, int CC = -1, bool commit = true, bool count = true) {
-  if (CC < 0) CC = C;
+                         int c_lo, int CC, bool commit, bool count) {
   for (int cc = threadIdx.x; cc < CC; cc += blockDim.x) {
     const int c = c_lo + cc;
     float mean, inv;
@@ -108,31 +107,54 @@ FEDMI_DEV void bn_coeffs(const BNArgs& a, int C, int M, float eps, float mom, in
         s1 += a.stats[(2 * r) * C + c];
         s2 += a.stats[(2 * r + 1) * C + c];
       }
-      const double msd = s1 / (double)M;   // mean of (z - shift)
-      const float ms = (float)msd;
-      const float var = (float)fmax(s2 / (double)M - msd * msd, 0.0);
-      mean = ms + (a.shift ? a.shift[c] : 0.f);
-      inv = rsqrtf(var + eps);
+      float ms, var;   // mean of (z - shift), biased variance
+      bn::bn_batch_stats(s1, s2, M, &ms, &var);
+      mean = bn::bn_unshift(ms, a.shift ? a.shift[c] : 0.f);
+      inv = bn::bn_inv_std(var, eps);
       if (commit) {
         a.smean[c] = mean;
         a.sinv[c] = inv;
         if (a.rmean) {
-          a.rmean[c] = (1.f - mom) * a.rmean[c] + mom * (mean + (a.cbias ? a.cbias[c] : 0.f));
-          a.rvar[c] = (1.f - mom) * a.rvar[c] + mom * var * ((float)M / (float)max(M - 1, 1));
+          a.rmean[c] = bn::bn_running_mean(mom, a.rmean[c], mean, a.cbias ? a.cbias[c] : 0.f);
+          a.rvar[c] = bn::bn_running_var(mom, a.rvar[c], var, M);
         }
       }
     } else {
-      mean = a.rmean[c] - (a.cbias ? a.cbias[c] : 0.f);
-      inv = rsqrtf(a.rvar[c] + eps);
+      mean = bn::bn_eval_mean(a.rmean[c], a.cbias ? a.cbias[c] : 0.f);
+      inv = bn::bn_inv_std(a.rvar[c], eps);
     }
-    sc[cc] = a.gamma[c] * inv;
-    sh[cc] = a.beta[c] - mean * sc[cc];
+    sc[cc] = bn::bn_scale(a.gamma[c], inv);
+    sh[cc] = bn::bn_shift(a.beta[c], mean, sc[cc]);
   }
   if (train && commit && count && threadIdx.x == 0 && a.nbt) a.nbt[0] += 1;
 }
 
-// BN scale / shift only ([2][C] fp32), with bn_apply's running-stat / saved-stat commit: for a BN whose
-// consumer applies it on load (bn_apply's output is never written).  One workgroup.
+// The forward prologue of both grids: the coefficients of channels [c_lo, c_lo + CC) into co[q * cs + cc]
+// (q = scA, shA, scB, shB), BN-A's copied to co_out by the commit blocks; ends with the block's barrier.
+FEDMI_DEV void bn_fwd_coeffs(const BNArgs& A, const BNArgs& B, int C, int M, float eps, float mom, int train,
+                             int res_mode, float* co, int cs, int c_lo, int CC, bool commit, bool count,
+                             float* co_out) {
+  bn_coeffs(A, C, M, eps, mom, train, co, co + cs, c_lo, CC, commit, count);
+  if (res_mode == 2) bn_coeffs(B, C, M, eps, mom, train, co + 2 * cs, co + 3 * cs, c_lo, CC, commit, count);
+  if (co_out != nullptr && commit)   // the coefficients, for a backward that derives the ReLU mask from z
+    for (int cc = threadIdx.x; cc < CC; cc += blockDim.x) {
+      co_out[c_lo + cc] = co[cc];
+      co_out[C + c_lo + cc] = co[cs + cc];
+    }
+  __syncthreads();
+}
+
+// One 8-channel vector of the forward, in place: v = act(bnA(v) [+ t | + bnB(t)]).  co: the four coefficient
+// rows of these 8 channels at stride cs (LDS or registers).
+FEDMI_DEV void bn_fwd_vec(float* v, const float* t, const float* co, int cs, int res_mode, int relu) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {   // selects, not branches: the modes are uniform and the extra fma is free here
+    const float x = bn::bn_affine(v[j], co[j], co[cs + j]);
+    const float r = res_mode == 2 ? bn::bn_affine(t[j], co[2 * cs + j], co[3 * cs + j]) : t[j];
+    const float s = res_mode ? bn::bn_add(x, r) : x;
+    v[j] = relu ? bn::bn_relu(s) : s;
+  }
+}
 
 // Channel-chunked grid of the apply kernels: blockIdx.y = chunk of CC <= 64 channels, blockIdx.x = chunk
 // of rows.  A block derives the BN coefficients of ITS channels only (16 fp64 replica reads x 2 per
@@ -148,44 +170,21 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16* __restrict__ 
                                                        int M, int C, float eps, float mom, int train, int relu,
                                                        int res_mode, int ldy, float* __restrict__ co_out) {
   extern __shared__ float co[];   // [4][C]
-  float* sc = co;
-  float* sh = co + C;
-  float* sc2 = co + 2 * C;
-  float* sh2 = co + 3 * C;
-  bn_coeffs(A, C, M, eps, mom, train, sc, sh, 0, C, blockIdx.x == 0);
-  if (res_mode == 2) bn_coeffs(B, C, M, eps, mom, train, sc2, sh2, 0, C, blockIdx.x == 0);
-  if (co_out != nullptr && blockIdx.x == 0)   // the coefficients, for a backward that derives the ReLU mask from z
-    for (int c = threadIdx.x; c < C; c += blockDim.x) { co_out[c] = sc[c]; co_out[C + c] = sh[c]; }
-  __syncthreads();
+  bn_fwd_coeffs(A, B, C, M, eps, mom, train, res_mode, co, C, 0, C, blockIdx.x == 0, true, co_out);
+  const bf16* tsrc = res_mode == 1 ? res : z2;
   const int VR = C >> 3;
   const long nv = (long)M * VR;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
     const int c0 = (int)(i % VR) * 8;
-    float v[8];
+    float v[8], t[8] = {};
     load8f(z + i * 8, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[c0 + j] + sh[c0 + j];
-    if (res_mode == 1) {
-      float r[8];
-      load8f(res + i * 8, r);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] += r[j];
-    } else if (res_mode == 2) {
-      float r[8];
-      load8f(z2 + i * 8, r);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] += r[j] * sc2[c0 + j] + sh2[c0 + j];
-    }
-    if (relu) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-    }
+    if (res_mode) load8f(tsrc + i * 8, t);
+    bn_fwd_vec(v, t, co + c0, C, res_mode, relu);
     store8f(y + (ldy == C ? i * 8 : (i / VR) * ldy + c0), v);
   }
 }
 
-// y = act(bnA(z) [+ res | + bnB(z2)])      res_mode: 0 none, 1 identity residual, 2 second BN branch
-// y rows have stride ldy (>= C): a channel slice of a concatenated output (GoogLeNet)
+// The same on the channel-chunked grid (C >= 256, C % 64 == 0).
 __global__ __launch_bounds__(256) void bn_apply_chunk_kernel(const bf16* __restrict__ z, BNArgs A,
                                                              const bf16* __restrict__ z2, BNArgs B,
                                                              const bf16* __restrict__ res, bf16* __restrict__ y, int M,
@@ -194,47 +193,36 @@ __global__ __launch_bounds__(256) void bn_apply_chunk_kernel(const bf16* __restr
                                                              float* __restrict__ co_out) {
   __shared__ float co[4][kBnChunk];
   const int CC = min(kBnChunk, C), c_lo = blockIdx.y * CC;
-  const bool commit = blockIdx.x == 0;
-  bn_coeffs(A, C, M, eps, mom, train, co[0], co[1], c_lo, CC, commit, blockIdx.y == 0);
-  if (res_mode == 2) bn_coeffs(B, C, M, eps, mom, train, co[2], co[3], c_lo, CC, commit, blockIdx.y == 0);
-  if (co_out != nullptr && commit)
-    for (int cc = threadIdx.x; cc < CC; cc += blockDim.x) { co_out[c_lo + cc] = co[0][cc]; co_out[C + c_lo + cc] = co[1][cc]; }
-  __syncthreads();
+  bn_fwd_coeffs(A, B, C, M, eps, mom, train, res_mode, &co[0][0], kBnChunk, c_lo, CC, blockIdx.x == 0,
+                blockIdx.y == 0, co_out);
+  const bf16* tsrc = res_mode == 1 ? res : z2;
   const int VC = CC >> 3, rstep = 256 / VC;
   const int cv = threadIdx.x % VC, c0 = cv * 8, cg = c_lo + c0;
   const int rb = blockIdx.x * rows_per_block, re = min(M, rb + rows_per_block);
   if ((int)threadIdx.x >= rstep * VC) return;
-  float sa[8], ha[8], sb[8], hb[8];
+  float cr[4][8];   // this thread's channels' coefficients, in registers
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    sa[j] = co[0][c0 + j]; ha[j] = co[1][c0 + j];
-    sb[j] = res_mode == 2 ? co[2][c0 + j] : 0.f; hb[j] = res_mode == 2 ? co[3][c0 + j] : 0.f;
-  }
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) cr[q][j] = q < 2 || res_mode == 2 ? co[q][c0 + j] : 0.f;
   // two rows per thread-slot, every load issued before the first use (the kernel is latency-bound on
   // the small late layers)
   for (int r0 = rb + (int)threadIdx.x / VC; r0 < re; r0 += 2 * rstep) {
-    float v[2][8], t[2][8];
+    float v[2][8], t[2][8] = {};
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = r0 + u * rstep;
       if (r < re) {
         const long i = (long)r * C + cg;
         load8f(z + i, v[u]);
-        if (res_mode == 1) load8f(res + i, t[u]);
-        else if (res_mode == 2) load8f(z2 + i, t[u]);
+        if (res_mode) load8f(tsrc + i, t[u]);
       }
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = r0 + u * rstep;
       if (r >= re) continue;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float x = v[u][j] * sa[j] + ha[j];
-        if (res_mode == 1) x += t[u][j];
-        else if (res_mode == 2) x += t[u][j] * sb[j] + hb[j];
-        v[u][j] = relu ? fmaxf(x, 0.f) : x;
-      }
+      bn_fwd_vec(v[u], t[u], &cr[0][0], 8, res_mode, relu);
       store8f(y + (long)r * ldy + cg, v[u]);
     }
   }
@@ -261,25 +249,34 @@ struct BwdIn {
                           // forward never materialised y (its consumer applied this BN on load)
 };
 
-// row r, channel group cg (8 channels); z: the 8 za values of the row (for the msc mask)
-FEDMI_DEV void load_g(const BwdIn& in, long r, int cg, float* g, const float* z) {
-  const long od = r * in.ldd + cg * 8;
-  load8f(in.dya + od, g);
+// Raw operands of one 8-channel vector of the BN backward (row r, channel offset c; i = the compact element index
+// r * C + c; dadd: BwdOut's, null in the reduce pass), all loads issued together; bwd_g then forms g from them.
+// The apply kernels issue their first vector this way BEFORE the coefficient prologue, so its latency overlaps
+// the fp64 channel-sum reads.
+struct BwdRaw {
+  float z[8], g[8], gb[8], ym[8], zb[8], da[8];
+};
+FEDMI_DEV void bwd_issue(const BwdIn& in, const bf16* dadd, long r, int c, long i, BwdRaw& x, bool zb = true) {
+  load8f(in.za + i, x.z);
+  const long od = r * in.ldd + c;
+  load8f(in.dya + od, x.g);
+  if (in.dyb) load8f(in.dyb + od, x.gb);
+  if (in.y) load8f(in.y + r * in.ldy + c, x.ym);
+  if (zb && in.zb) load8f(in.zb + i, x.zb);
+  if (dadd) load8f(dadd + i, x.da);
+}
+FEDMI_DEV void bwd_g(const BwdIn& in, int c, BwdRaw& x) {
   if (in.dyb) {
-    float t[8];
-    load8f(in.dyb + od, t);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] += t[j];
+    for (int j = 0; j < 8; ++j) x.g[j] += x.gb[j];
   }
   if (in.y) {
-    float t[8];
-    load8f(in.y + r * in.ldy + cg * 8, t);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] = t[j] > 0.f ? g[j] : 0.f;
+    for (int j = 0; j < 8; ++j) x.g[j] = x.ym[j] > 0.f ? x.g[j] : 0.f;
   } else if (in.msc) {
     const int C = in.ldd;   // msc mode: compact rows (host checks ldd == C)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] = z[j] * in.msc[cg * 8 + j] + in.msc[C + cg * 8 + j] > 0.f ? g[j] : 0.f;
+    for (int j = 0; j < 8; ++j) x.g[j] = bn::bn_affine(x.z[j], in.msc[c + j], in.msc[C + c + j]) > 0.f ? x.g[j] : 0.f;
   }
 }
 
@@ -307,19 +304,19 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(BwdIn in, double* __
   for (int j = 0; j < 8; ++j) s0[j] = s1[j] = s2[j] = 0.f;
   const int rb = blockIdx.x * rows_per_block, re = min(M, rb + rows_per_block);
   for (int r = rb + r0; r < re; r += rstep) {
-    const long i = (long)r * VR + cg;
-    float g[8], z[8];
-    load8f(in.za + i * 8, z);
-    load_g(in, r, cg, g, z);
+    BwdRaw x;
+    const long i = (long)r * C + c0;
+    bwd_issue(in, nullptr, r, c0, i, x, false);   // zb after branch A's terms: its registers are z's
+    bwd_g(in, c0, x);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      s0[j] += g[j];
-      s1[j] += g[j] * (z[j] - ma[j]) * ia[j];
+      s0[j] += x.g[j];
+      s1[j] = bn::bn_sum_term(s1[j], x.g[j], x.z[j], ma[j], ia[j]);
     }
     if (in.zb) {
-      load8f(in.zb + i * 8, z);
+      load8f(in.zb + i, x.zb);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) s2[j] += g[j] * (z[j] - mb[j]) * ib[j];
+      for (int j = 0; j < 8; ++j) s2[j] = bn::bn_sum_term(s2[j], x.g[j], x.zb[j], mb[j], ib[j]);
     }
   }
 #pragma unroll
@@ -373,57 +370,20 @@ struct BwdOut {
   const bf16* dadd;       // optional grad added to dza (a residual edge that bypasses this BN)
 };
 
-// Raw operands of one 8-channel vector of the BN backward (row r, channel offset c; i = the compact element index
-// r * C + c), all loads issued together; bwd_g then forms load_g's g from them.  The apply kernels issue their
-// first vector this way BEFORE the coefficient prologue, so its latency overlaps the fp64 channel-sum reads.
-struct BwdRaw {
-  float z[8], g[8], gb[8], ym[8], zb[8], da[8];
-};
-FEDMI_DEV void bwd_issue(const BwdIn& in, const BwdOut& out, long r, int c, long i, BwdRaw& x) {
-  load8f(in.za + i, x.z);
-  const long od = r * in.ldd + c;
-  load8f(in.dya + od, x.g);
-  if (in.dyb) load8f(in.dyb + od, x.gb);
-  if (in.y) load8f(in.y + r * in.ldy + c, x.ym);
-  if (in.zb) load8f(in.zb + i, x.zb);
-  if (out.dadd) load8f(out.dadd + i, x.da);
-}
-FEDMI_DEV void bwd_g(const BwdIn& in, int c, BwdRaw& x) {
-  if (in.dyb) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x.g[j] += x.gb[j];
-  }
-  if (in.y) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x.g[j] = x.ym[j] > 0.f ? x.g[j] : 0.f;
-  } else if (in.msc) {
-    const int C = in.ldd;   // msc mode: compact rows (host checks ldd == C)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x.g[j] = x.z[j] * in.msc[c + j] + in.msc[C + c + j] > 0.f ? x.g[j] : 0.f;
-  }
-}
-
-// Flat grid variant (see bn_apply_kernel).
-// partials != null (chained mode): the channel sums are read straight from the reduce kernel's
-// 'reps' atomic replicas (no finalize launch); the caller zeroes them before the next step.
-__global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(BwdIn in, BwdOut out, const double* __restrict__ red,
-                                                           int M, int C, const double* __restrict__ partials,
-                                                           int reps) {
-  extern __shared__ float co[];   // [6][C]: kA, bA, cA, kB, bB, cB  (dz = k*g + b*xhat + c)
-  const float invM = 1.f / (float)M;
-  const int VR = C >> 3;
-  const int nv = M * VR;          // host: < 2^31
-  const int stride = gridDim.x * blockDim.x;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  BwdRaw x;
-  if (i < nv) {
-    const int row = i / VR;
-    bwd_issue(in, out, row, (i - row * VR) * 8, (long)i * 8, x);
-  }
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+// The backward prologue of both grids: the channel sums of channels [c_lo, c_lo + CC) -- from red, or
+// (partials != null, chained mode) summed in fixed order from the 'reps' replicas, so every block derives
+// identical coefficients -- into co[q * cs + cc], q = kA, bA, cA, kB, bB, cB (dz = k * g + b * z + c); the
+// commit blocks write dgamma / dbeta and this step's batch mean as the next step's statistics shift.
+// Ends with the block's barrier.
+FEDMI_DEV void bn_bwd_coeffs(const BwdIn& in, const BwdOut& out, const double* __restrict__ red,
+                             const double* __restrict__ partials, int reps, int M, int C, float* co, int cs, int c_lo,
+                             int CC, bool commit) {
+  const float invM = bn::bn_inv_count(M);
+  for (int cc = threadIdx.x; cc < CC; cc += blockDim.x) {
+    const int c = c_lo + cc;
     double dg = 0.0, dgx = 0.0, dgx2 = 0.0;
     if (partials) {
-      for (int r = 0; r < reps; ++r) {           // fixed order: every block derives identical coefficients
+      for (int r = 0; r < reps; ++r) {
         const double* pr = partials + (long)r * 3 * C;
         dg += pr[c];
         dgx += pr[C + c];
@@ -434,60 +394,74 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(BwdIn in, BwdOut
       dgx = red[C + c];
       if (in.zb) dgx2 = red[2 * C + c];
     }
-    const float sg = (float)dg, sgx = (float)dgx, sgx2 = (float)dgx2;
-    const float scA = out.gammaA[c] * in.invA[c];
-    // dz = scA * (g - sg/M - xhat * sgx/M),  xhat = (z - mean) * inv
-    co[c] = scA;
-    co[C + c] = -scA * sgx * invM * in.invA[c];
-    co[2 * C + c] = -scA * sg * invM + scA * sgx * invM * in.invA[c] * in.meanA[c];
-    if (blockIdx.x == 0) {
-      out.dgammaA[c] = sgx;
-      out.dbetaA[c] = sg;
-      if (out.shiftA) out.shiftA[c] = in.meanA[c];
-    }
-    if (in.zb) {
-      const float scB = out.gammaB[c] * in.invB[c];
-      co[3 * C + c] = scB;
-      co[4 * C + c] = -scB * sgx2 * invM * in.invB[c];
-      co[5 * C + c] = -scB * sg * invM + scB * sgx2 * invM * in.invB[c] * in.meanB[c];
-      if (blockIdx.x == 0) {
-        out.dgammaB[c] = sgx2;
-        out.dbetaB[c] = sg;
-        if (out.shiftB) out.shiftB[c] = in.meanB[c];
+    const float sg = (float)dg;
+    auto branch = [&](float* cq, float sgx, const float* gamma, const float* mean, const float* inv, float* dgamma,
+                      float* dbeta, float* shift) {
+      const float k = bn::bn_scale(gamma[c], inv[c]);
+      const float b = bn::bn_bwd_b(k, sgx, invM, inv[c]);
+      cq[cc] = k;
+      cq[cs + cc] = b;
+      cq[2 * cs + cc] = bn::bn_bwd_c(k, sg, invM, b, mean[c]);
+      if (commit) {
+        dgamma[c] = sgx;
+        dbeta[c] = sg;
+        if (shift) shift[c] = mean[c];
       }
-    }
+    };
+    branch(co, (float)dgx, out.gammaA, in.meanA, in.invA, out.dgammaA, out.dbetaA, out.shiftA);
+    if (in.zb) branch(co + 3 * cs, (float)dgx2, out.gammaB, in.meanB, in.invB, out.dgammaB, out.dbetaB, out.shiftB);
   }
   __syncthreads();
-  for (bool first = true; i < nv; i += stride, first = false) {
-    const int row = i / VR, c0 = (i - row * VR) * 8;
-    if (!first) bwd_issue(in, out, row, c0, (long)i * 8, x);
-    bwd_g(in, c0, x);
-    if (out.gout) store8f(out.gout + (long)i * 8, x.g);
-    float d[8];
+}
+
+// One 8-channel vector of the backward: x (as issued) -> gout / dza / dzb at the compact element index i.
+// c: the vector's first channel; co: the six coefficient rows of these 8 channels at stride cs.
+FEDMI_DEV void bn_bwd_vec(const BwdIn& in, const BwdOut& out, int c, long i, BwdRaw& x, const float* co, int cs) {
+  bwd_g(in, c, x);
+  if (out.gout) store8f(out.gout + i, x.g);
+  float d[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) d[j] = co[c0 + j] * x.g[j] + co[C + c0 + j] * x.z[j] + co[2 * C + c0 + j];
-    if (out.dadd) {
+  for (int j = 0; j < 8; ++j) d[j] = bn::bn_dz(co[j], x.g[j], co[cs + j], x.z[j], co[2 * cs + j]);
+  if (out.dadd) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) d[j] += x.da[j];
-    }
-    store8f(out.dza + (long)i * 8, d);
-    if (in.zb) {
+    for (int j = 0; j < 8; ++j) d[j] = bn::bn_dz_add(d[j], x.da[j]);
+  }
+  store8f(out.dza + i, d);
+  if (in.zb) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) d[j] = co[3 * C + c0 + j] * x.g[j] + co[4 * C + c0 + j] * x.zb[j] + co[5 * C + c0 + j];
-      store8f(out.dzb + (long)i * 8, d);
-    }
+    for (int j = 0; j < 8; ++j) d[j] = bn::bn_dz(co[3 * cs + j], x.g[j], co[4 * cs + j], x.zb[j], co[5 * cs + j]);
+    store8f(out.dzb + i, d);
   }
 }
 
-// partials != null (chained mode): the channel sums are read straight from the reduce kernel's
-// 'reps' atomic replicas (no finalize launch); the caller zeroes them before the next step.
-// Channel-chunked grid like bn_apply_kernel: a block derives the coefficients of its CC channels only.
+// Flat grid (see bn_apply_kernel).
+__global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(BwdIn in, BwdOut out, const double* __restrict__ red,
+                                                           int M, int C, const double* __restrict__ partials,
+                                                           int reps) {
+  extern __shared__ float co[];   // [6][C]
+  const int VR = C >> 3;
+  const int nv = M * VR;          // host: < 2^31
+  const int stride = gridDim.x * blockDim.x;
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  BwdRaw x;
+  if (i < nv) {
+    const int row = i / VR;
+    bwd_issue(in, out.dadd, row, (i - row * VR) * 8, (long)i * 8, x);
+  }
+  bn_bwd_coeffs(in, out, red, partials, reps, M, C, co, C, 0, C, blockIdx.x == 0);
+  for (bool first = true; i < nv; i += stride, first = false) {
+    const int row = i / VR, c0 = (i - row * VR) * 8;
+    if (!first) bwd_issue(in, out.dadd, row, c0, (long)i * 8, x);
+    bn_bwd_vec(in, out, c0, (long)i * 8, x, co + c0, C);
+  }
+}
+
+// Channel-chunked grid (see bn_apply_chunk_kernel): a block derives the coefficients of its CC channels only.
 __global__ __launch_bounds__(256) void bn_bwd_apply_chunk_kernel(BwdIn in, BwdOut out, const double* __restrict__ red,
                                                                  int M, int C, const double* __restrict__ partials,
                                                                  int reps, int rows_per_block) {
-  __shared__ float co[6][kBnChunk];   // kA, bA, cA, kB, bB, cB  (dz = k*g + b*z + c)
+  __shared__ float co[6][kBnChunk];
   const int CC = min(kBnChunk, C), c_lo = blockIdx.y * CC;
-  const float invM = 1.f / (float)M;
   const int VC = CC >> 3, rstep = 256 / VC;
   const int cv = threadIdx.x % VC, c0 = cv * 8, cg = c_lo + c0;
   const int rb = blockIdx.x * rows_per_block, re = min(M, rb + rows_per_block);
@@ -498,72 +472,19 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_chunk_kernel(BwdIn in, BwdOu
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = r0 + u * rstep;
-      if (r < re) bwd_issue(in, out, r, cg, (long)r * C + cg, x[u]);
+      if (r < re) bwd_issue(in, out.dadd, r, cg, (long)r * C + cg, x[u]);
     }
   };
   int r0 = rb + (int)threadIdx.x / VC;
   if (lane_ok) issue_pair(r0);
-  for (int cc = threadIdx.x; cc < CC; cc += blockDim.x) {
-    const int c = c_lo + cc;
-    double dg = 0.0, dgx = 0.0, dgx2 = 0.0;
-    if (partials) {
-      for (int r = 0; r < reps; ++r) {           // fixed order: every block derives identical coefficients
-        const double* pr = partials + (long)r * 3 * C;
-        dg += pr[c];
-        dgx += pr[C + c];
-        if (in.zb) dgx2 += pr[2 * C + c];
-      }
-    } else {
-      dg = red[c];
-      dgx = red[C + c];
-      if (in.zb) dgx2 = red[2 * C + c];
-    }
-    const float sg = (float)dg, sgx = (float)dgx, sgx2 = (float)dgx2;
-    const float scA = out.gammaA[c] * in.invA[c];
-    // dz = scA * (g - sg/M - xhat * sgx/M),  xhat = (z - mean) * inv
-    co[0][cc] = scA;
-    co[1][cc] = -scA * sgx * invM * in.invA[c];
-    co[2][cc] = -scA * sg * invM + scA * sgx * invM * in.invA[c] * in.meanA[c];
-    if (blockIdx.x == 0) {
-      out.dgammaA[c] = sgx;
-      out.dbetaA[c] = sg;
-      if (out.shiftA) out.shiftA[c] = in.meanA[c];
-    }
-    if (in.zb) {
-      const float scB = out.gammaB[c] * in.invB[c];
-      co[3][cc] = scB;
-      co[4][cc] = -scB * sgx2 * invM * in.invB[c];
-      co[5][cc] = -scB * sg * invM + scB * sgx2 * invM * in.invB[c] * in.meanB[c];
-      if (blockIdx.x == 0) {
-        out.dgammaB[c] = sgx2;
-        out.dbetaB[c] = sg;
-        if (out.shiftB) out.shiftB[c] = in.meanB[c];
-      }
-    }
-  }
-  __syncthreads();
+  bn_bwd_coeffs(in, out, red, partials, reps, M, C, &co[0][0], kBnChunk, c_lo, CC, blockIdx.x == 0);
   if (!lane_ok) return;
   for (bool first = true; r0 < re; r0 += 2 * rstep, first = false) {
     if (!first) issue_pair(r0);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = r0 + u * rstep;
-      if (r >= re) continue;
-      const long i = (long)r * C + cg;
-      bwd_g(in, cg, x[u]);
-      if (out.gout) store8f(out.gout + i, x[u].g);
-      float d[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        d[j] = co[0][c0 + j] * x[u].g[j] + co[1][c0 + j] * x[u].z[j] + co[2][c0 + j];
-        if (out.dadd) d[j] += x[u].da[j];
-      }
-      store8f(out.dza + i, d);
-      if (in.zb) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) d[j] = co[3][c0 + j] * x[u].g[j] + co[4][c0 + j] * x[u].zb[j] + co[5][c0 + j];
-        store8f(out.dzb + i, d);
-      }
+      if (r < re) bn_bwd_vec(in, out, cg, (long)r * C + cg, x[u], &co[0][c0], kBnChunk);
     }
   }
 }
@@ -1141,7 +1062,8 @@ static void bn_bwd_grid(int M, int C, int* tb, int* rows_per_block, int* nblk) {
 }
 
 // Scratch (fp64 elements) the two-level reduction of launch_bn_bwd needs (ZERO-initialised
-// once by the caller; every launch leaves it zero again).
+// once by the caller; every launch leaves it zero again).  M is unused (the replicas are per channel);
+// it stays in the signature the Python callers and their emulation share.
 long bn_bwd_ws_floats(int M, int C) {
   (void)M;
   return (long)BN_REP * 3 * C;
@@ -1170,6 +1092,18 @@ void launch_bn_bwd(hipStream_t st, const BNBwdDesc& d, double* red, int M, int C
              d.dadd};
   int tb, rows_per_block, nblk;
   bn_bwd_grid(M, C, &tb, &rows_per_block, &nblk);
+  // the apply pass for this C; partials / reps: the chained replicas (null: the sums are in red)
+  auto apply = [&](const double* partials, int reps, long flat_cap) {
+    if (use_chunked(C)) {
+      const dim3 ag = apply_grid(M, C);
+      hipLaunchKernelGGL(bn_bwd_apply_chunk_kernel, ag, dim3(256), 0, st, in, out, red, M, C, partials, reps,
+                         (M + (int)ag.x - 1) / (int)ag.x);
+    } else {
+      const int gblk = (int)std::min<long>(((long)M * VR + 255) / 256, flat_cap);
+      hipLaunchKernelGGL(bn_bwd_apply_flat_kernel, dim3(gblk), dim3(256), 6 * C * sizeof(float), st, in, out, red, M,
+                         C, partials, reps);
+    }
+  };
   if (chained) {
     // ws: this BN's own replica buffer, ZERO on entry (the head kernel clears the arena every step)
     const int reps = bn_bwd_chain_reps(C);
@@ -1178,15 +1112,7 @@ void launch_bn_bwd(hipStream_t st, const BNBwdDesc& d, double* red, int M, int C
       throw std::invalid_argument("bn_bwd: presummed sums cover one incoming grad");
     if (!presummed)
       hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(tb), 0, st, in, red, M, C, rows_per_block, ws, reps);
-    if (use_chunked(C)) {
-      const dim3 ag = apply_grid(M, C);
-      hipLaunchKernelGGL(bn_bwd_apply_chunk_kernel, ag, dim3(256), 0, st, in, out, red, M, C, ws, reps,
-                         (M + (int)ag.x - 1) / (int)ag.x);
-    } else {
-      const int gblk = (int)std::min<long>(((long)M * VR + 255) / 256, 1024);
-      hipLaunchKernelGGL(bn_bwd_apply_flat_kernel, dim3(gblk), dim3(256), 6 * C * sizeof(float), st, in, out, red, M,
-                         C, ws, reps);
-    }
+    apply(ws, reps, 1024);
     return;
   }
   if (presummed) throw std::invalid_argument("bn_bwd: presummed needs chained replicas");
@@ -1194,14 +1120,7 @@ void launch_bn_bwd(hipStream_t st, const BNBwdDesc& d, double* red, int M, int C
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(tb), 0, st, in, red, M, C, rows_per_block,
                      two ? ws : nullptr, BN_REP);
   if (two) hipLaunchKernelGGL(bn_bwd_finalize, dim3((3 * C + 255) / 256), dim3(256), 0, st, ws, C, red);
-  if (use_chunked(C)) {
-    const dim3 ag = apply_grid(M, C);
-    hipLaunchKernelGGL(bn_bwd_apply_chunk_kernel, ag, dim3(256), 0, st, in, out, red, M, C, nullptr, 0,
-                       (M + (int)ag.x - 1) / (int)ag.x);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_apply_flat_kernel, dim3(grid_for((long)M * VR)), dim3(256), 6 * C * sizeof(float), st,
-                       in, out, red, M, C, nullptr, 0);
-  }
+  apply(nullptr, 0, 2048);   // grid_for's cap
 }
 
 void launch_head(hipStream_t st, const bf16* y, const int* labels, int base, const int* dbase, int N, int HW, int C, int J,

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bn_math.h"
+
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -97,37 +99,30 @@ struct BnSums {
   int msc_ld;           // C (row stride of msc)
 };
 
-// one 8-channel group of a DGRAD output row into the BN-backward sums (bm/bi: [2][8] mean / inv of
-// the two branches; q: [3][8])
-// the same on operands already in registers (an epilogue that prefetched its rows' z / y / zb)
+// one 8-channel group of a DGRAD output row into the BN-backward sums (bm / bi: [3][8], see bnsum_coeffs;
+// q: [3][8]), on operands already in registers (an epilogue that prefetched its rows' z / y / zb).  The mask and
+// the terms are bn_math.h's: the same bits as bn_bwd_reduce_kernel takes for the same element.
 FEDMI_DEV void bnsum_acc_v(const BnSums& bs, const bf16x8& t, const bf16x8& z, const bf16x8& y, const bf16x8& zb,
                            const float (*bm)[8], const float (*bi)[8], float (*q)[8]) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     float g = (float)t[j];
     if (bs.y && !((float)y[j] > 0.f)) g = 0.f;
-    else if (!bs.y && bs.msc && !((float)z[j] * bm[2][j] + bi[2][j] > 0.f)) g = 0.f;
+    else if (!bs.y && bs.msc && !(bn::bn_affine((float)z[j], bm[2][j], bi[2][j]) > 0.f)) g = 0.f;
     q[0][j] += g;
-    q[1][j] += g * ((float)z[j] - bm[0][j]) * bi[0][j];
-    if (bs.zb) q[2][j] += g * ((float)zb[j] - bm[1][j]) * bi[1][j];
+    q[1][j] = bn::bn_sum_term(q[1][j], g, (float)z[j], bm[0][j], bi[0][j]);
+    if (bs.zb) q[2][j] = bn::bn_sum_term(q[2][j], g, (float)zb[j], bm[1][j], bi[1][j]);
   }
 }
 
+// the same, loading the operands of compact element index idx
 FEDMI_DEV void bnsum_acc(const BnSums& bs, long idx, const bf16x8& t, const float (*bm)[8], const float (*bi)[8],
-                         float (*q)[8]) {   // bm / bi: [3][8] (see bnsum_coeffs)
+                         float (*q)[8]) {
   const bf16x8 z = *reinterpret_cast<const bf16x8*>(bs.z + idx);
   bf16x8 y{}, zb{};
   if (bs.y) y = *reinterpret_cast<const bf16x8*>(bs.y + idx);
   if (bs.zb) zb = *reinterpret_cast<const bf16x8*>(bs.zb + idx);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float g = (float)t[j];
-    if (bs.y && !((float)y[j] > 0.f)) g = 0.f;
-    else if (!bs.y && bs.msc && !((float)z[j] * bm[2][j] + bi[2][j] > 0.f)) g = 0.f;
-    q[0][j] += g;
-    q[1][j] += g * ((float)z[j] - bm[0][j]) * bi[0][j];
-    if (bs.zb) q[2][j] += g * ((float)zb[j] - bm[1][j]) * bi[1][j];
-  }
+  bnsum_acc_v(bs, t, z, y, zb, bm, bi, q);
 }
 
 // mean / inv of an 8-channel group (both branches; [2]: the z-mask scale / shift), zero past the last channel

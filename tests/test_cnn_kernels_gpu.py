@@ -1,9 +1,11 @@
 """Implicit-GEMM conv (fwd / dgrad / wgrad), BatchNorm fwd/bwd and the
 classifier head vs PyTorch fp32 references on the same bf16-rounded inputs."""
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import bn_check
 from fedmi.ops import cnn, conv
 
 pytestmark = pytest.mark.gpu
@@ -1002,3 +1004,292 @@ def test_bn_bwd_z_mask_at_rounding_distance_is_the_fused_sign(gpu_device):
     torch.cuda.synchronize()
     assert float(((db2.double() - s0).abs() / scale).max()) < 1e-5
     assert _rel(dz2.float(), ref.float()) < 1e-2
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# BatchNorm against the exact reference of csrc/kernels/bn_math.h (tests/bn_check.py): bit for bit.  The channel
+# sums are written by the test (forward: ``stats``; backward: chained + presummed replicas), or are exact in any
+# order (dyadic data), so no accumulation order enters.
+# ---------------------------------------------------------------------------------------------------------------
+def _np(t):
+    return t.detach().float().cpu().numpy() if t.dtype == torch.bfloat16 else t.detach().cpu().numpy()
+
+
+def _eq(got, want, what):
+    want = torch.from_numpy(np.ascontiguousarray(want)).to(got.dtype)
+    got = got.detach().cpu()
+    assert torch.equal(got, want), (what, int((got != want).sum()), got.numel())
+
+
+def _bn_params(C, M, z, g, dev, train, cbias, shifted):
+    """One BN's tensors + their numpy twins.  train: ``stats`` = fp64 sums of (z - shift) spread unevenly over the
+    replicas."""
+    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.3
+    rmean, rvar = torch.randn(C, generator=g) * 0.2, torch.rand(C, generator=g) + 0.5
+    cb = torch.randn(C, generator=g) * 0.1 if cbias else None
+    shift = torch.randn(C, generator=g) * 0.1 if shifted else None
+    stats = None
+    if train:
+        d = z.double() - (shift.double() if shifted else 0.0)
+        w = torch.arange(1, conv.STAT_REP + 1, dtype=torch.float64)
+        stats = (torch.stack([d.sum(0), (d * d).sum(0)]) * (w / w.sum()).view(-1, 1, 1)).contiguous()
+    host = dict(stats=stats, gamma=gamma, beta=beta, rmean=rmean, rvar=rvar, shift=shift, cbias=cb)
+    devt = {k: (v.to(dev) if v is not None else None) for k, v in host.items()}
+    desc = cnn.bn_desc(devt["stats"], devt["gamma"], devt["beta"], devt["rmean"], devt["rvar"],
+                       torch.zeros(1, dtype=torch.int64, device=dev), torch.empty(C, device=dev),
+                       torch.empty(C, device=dev), devt["shift"], devt["cbias"])
+    return desc, {k: (v.numpy().copy() if v is not None else None) for k, v in host.items()}
+
+
+# (M, C, res_mode, relu, train, ldy - C, cbias): C 8 / 24 / 192 take the flat grid, 256 / 320 the chunked one; M = 3:
+# fewer rows than one row pass; M = 65 = 2 * rstep + 1 (chunked: rstep = 32): the second row of a pair out of range;
+# the last of each grid: one M just past the grid's cap, so a block loops
+BN_FWD_CASES = [(3, 8, 0, True, True, 0, False), (65, 24, 1, False, True, 16, True), (65, 192, 2, True, True, 0, False),
+                (65, 24, 0, True, False, 0, True), (2048 * 256 + 5, 8, 1, True, True, 0, False),
+                (3, 256, 2, True, True, 0, True), (65, 320, 1, True, True, 64, False), (65, 256, 0, False, False, 0, True),
+                (65, 320, 2, False, True, 0, False), (32768 + 65, 256, 0, True, True, 0, False)]
+
+
+def _bn_fwd_run(dev, case, eps=1e-5, mom=0.1):
+    """Runs bn_apply on a case's inputs -> (device outputs, host inputs)."""
+    M, C, res_mode, relu, train, pad, cbias = case
+    g = torch.Generator(device="cpu").manual_seed(100 + C + M % 7)
+    z = (torch.randn(M, C, generator=g) * 2 + 0.5).bfloat16()
+    t = torch.randn(M, C, generator=g).bfloat16() if res_mode else None
+    A, hA = _bn_params(C, M, z, g, dev, train, cbias, shifted=train)
+    B, hB = _bn_params(C, M, t, g, dev, train, cbias, shifted=False) if res_mode == 2 else (None, None)
+    ybuf = torch.zeros(M, C + pad, dtype=torch.bfloat16, device=dev)
+    y = ybuf[:, 8:8 + C] if pad else ybuf
+    co = torch.empty(2, C, device=dev)
+    cnn.bn_apply(z.to(dev), A, y, train=train, relu=relu, z2=t.to(dev) if res_mode == 2 else None, b=B,
+                 res=t.to(dev) if res_mode == 1 else None, eps=eps, momentum=mom, co_out=co)
+    torch.cuda.synchronize()
+    return dict(y=y, ybuf=ybuf, co=co, A=A, B=B), dict(z=z, t=t, hA=hA, hB=hB)
+
+
+@pytest.mark.parametrize("case", BN_FWD_CASES, ids=[str(c) for c in BN_FWD_CASES])
+def test_bn_apply_is_bn_math_bit_for_bit(gpu_device, case):
+    M, C, res_mode, relu, train, pad, cbias = case
+    eps, mom = 1e-5, 0.1
+    out, inp = _bn_fwd_run(gpu_device, case, eps, mom)
+    y, ybuf, co, A, B = (out[k] for k in ("y", "ybuf", "co", "A", "B"))
+    z, t, hA, hB = (inp[k] for k in ("z", "t", "hA", "hB"))
+    yr, ca, cb = bn_check.forward(_np(z), hA, M, eps, mom, train, relu, res=_np(t) if res_mode == 1 else None,
+                                  z2=_np(t) if res_mode == 2 else None, B=hB)
+    _eq(y, yr, "y")
+    _eq(co, np.stack([ca["sc"], ca["sh"]]), "co_out")
+    for desc, c in ((A, ca), (B, cb)):
+        if desc is not None and train:
+            _eq(desc.smean, c["smean"], "smean"), _eq(desc.sinv, c["sinv"], "sinv")
+            _eq(desc.rmean, c["rmean"], "rmean"), _eq(desc.rvar, c["rvar"], "rvar")
+    if pad:
+        assert float(ybuf[:, :8].float().abs().max()) == 0.0 and float(ybuf[:, 8 + C:].float().abs().max()) == 0.0
+    assert int(A.nbt.item()) == int(train)
+
+
+def _dyadic(shape, g, step, bound):
+    n = int(bound / step)
+    return torch.randint(-n, n + 1, shape, generator=g).float() * step
+
+
+# (M, C, mask, dyb, zb, gout, dadd, ldd - C): as BN_FWD_CASES; chained mode caps the flat grid at 1024 blocks.  The dyb
+# cases run the reduce kernel (presummed sums cover one incoming grad) on dyadic data: their sums are exact in fp32.
+BN_BWD_CASES = [(3, 8, "y", False, False, True, False, 0), (65, 24, "bn", False, True, False, True, 0),
+                (65, 192, None, True, False, True, False, 0), (65, 24, "y", False, True, False, True, 16),
+                (2048 * 256 + 5, 8, "bn", False, False, False, False, 0),
+                (3, 256, "bn", False, True, False, True, 0), (65, 320, "y", False, False, True, False, 64),
+                (65, 256, None, True, True, True, False, 0), (65, 320, "bn", False, True, True, True, 0),
+                (32768 + 65, 256, "y", False, False, False, True, 0)]
+
+
+def _bn_bwd_run(dev, case):
+    """Runs bn_bwd (chained) on a case's inputs -> (device outputs, host inputs)."""
+    M, C, mask, use_dyb, use_zb, use_gout, use_dadd, pad = case
+    g = torch.Generator(device="cpu").manual_seed(200 + C + M % 7)
+    if use_dyb:
+        # bit budget: g = dya + dyb is a multiple of 1/4 <= 8, z - mean a multiple of 1/8 <= 5, inv a power of two <= 2:
+        # a term is a multiple of 1/64 <= 80, a sum over M = 65 rows < 2^13 * 64 = 2^19 quanta -- exact in fp32's 24 bits
+        assert M <= 65
+        rnd = lambda: _dyadic((M, C), g, 0.25, 4.0).bfloat16()
+        zs = lambda: _dyadic((M, C), g, 0.125, 4.0).bfloat16()
+        stat = lambda: (_dyadic((C,), g, 0.125, 1.0), torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=g)])
+    else:
+        rnd = lambda: torch.randn(M, C, generator=g).bfloat16()
+        zs = lambda: (torch.randn(M, C, generator=g) * 2 + 0.5).bfloat16()
+        stat = lambda: (torch.randn(C, generator=g) * 0.2, torch.rand(C, generator=g) + 0.5)
+    dya, dyb = rnd(), rnd() if use_dyb else None
+    za, zb = zs(), zs() if use_zb else None
+    dadd = rnd() if use_dadd else None
+    (meanA, invA), (meanB, invB) = stat(), stat()
+    gammaA, gammaB = torch.rand(C, generator=g) + 0.5, torch.rand(C, generator=g) + 0.5
+    y = torch.relu(torch.randn(M, C, generator=g)).bfloat16() if mask == "y" else None
+    msc = torch.stack([torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.5]) if mask == "bn" else None
+    gm = bn_check.masked_grad(_np(dya), _np(dyb) if use_dyb else None, _np(y) if y is not None else None, _np(za),
+                              msc.numpy() if msc is not None else None)
+    # the channel sums, in fp64 (exact for the dyadic cases; what a DGRAD epilogue would have added otherwise)
+    gd = torch.from_numpy(gm).double()
+    sums = torch.stack([gd.sum(0), (gd * ((za.double() - meanA.double()) * invA.double())).sum(0),
+                        (gd * ((zb.double() - meanB.double()) * invB.double())).sum(0) if use_zb else torch.zeros(C).double()])
+    reps = cnn.bn_bwd_chain_floats(C) // (3 * C)
+    w = torch.arange(1, reps + 1, dtype=torch.float64)
+    rep_host = (sums * (w / w.sum()).view(-1, 1, 1)).contiguous()
+    rep = torch.zeros_like(rep_host).to(dev) if use_dyb else rep_host.to(dev)
+
+    def wide(t):   # a channel slice of a wider buffer (ldd > C)
+        if t is None or not pad:
+            return t.to(dev) if t is not None else None
+        buf = torch.zeros(M, C + pad, dtype=t.dtype, device=dev)
+        buf[:, 8:8 + C] = t.to(dev)
+        return buf[:, 8:8 + C]
+
+    a = cnn.bn_desc(gamma=gammaA.to(dev), smean=meanA.to(dev), sinv=invA.to(dev), shift=torch.empty(C, device=dev))
+    b = cnn.bn_desc(gamma=gammaB.to(dev), smean=meanB.to(dev), sinv=invB.to(dev), shift=torch.empty(C, device=dev)) if use_zb else None
+    dg, db, dg2, db2 = (torch.empty(C, device=dev) for _ in range(4))
+    dza, dzb, gout = (torch.full((M, C), float("nan"), dtype=torch.bfloat16, device=dev) for _ in range(3))
+    red = torch.zeros(3, C, dtype=torch.float64, device=dev)
+    cnn.bn_bwd(wide(dya), za.to(dev), a, dg, db, dza, red, dyb=wide(dyb), y=wide(y), zb=zb.to(dev) if use_zb else None, b=b,
+               dgamma_b=dg2 if use_zb else None, dbeta_b=db2 if use_zb else None, dzb=dzb if use_zb else None,
+               gout=gout if use_gout else None, ws=rep.view(-1), dadd=dadd.to(dev) if use_dadd else None, chained=True,
+               mask_bn=msc.to(dev) if msc is not None else None, presummed=not use_dyb)
+    torch.cuda.synchronize()
+    return (dict(dza=dza, dzb=dzb, gout=gout, dg=dg, db=db, dg2=dg2, db2=db2, a=a, b=b, rep=rep),
+            dict(gm=gm, sums=sums, rep_host=rep_host, reps=reps, za=za, zb=zb, dadd=dadd, gammaA=gammaA, gammaB=gammaB,
+                 meanA=meanA, meanB=meanB, invA=invA, invB=invB, msc=msc))
+
+
+@pytest.mark.parametrize("case", BN_BWD_CASES, ids=[str(c) for c in BN_BWD_CASES])
+def test_bn_bwd_apply_is_bn_math_bit_for_bit(gpu_device, case):
+    M, C, mask, use_dyb, use_zb, use_gout, use_dadd, pad = case
+    out, inp = _bn_bwd_run(gpu_device, case)
+    dza, dzb, gout, dg, db, dg2, db2, a, b, rep = (out[k] for k in ("dza", "dzb", "gout", "dg", "db", "dg2", "db2", "a", "b", "rep"))
+    gm, sums, rep_host, reps, za, zb, dadd = (inp[k] for k in ("gm", "sums", "rep_host", "reps", "za", "zb", "dadd"))
+    gammaA, gammaB, meanA, meanB, invA, invB = (inp[k] for k in ("gammaA", "gammaB", "meanA", "meanB", "invA", "invB"))
+    if use_dyb:   # the reduce kernel's sums, in whatever order its atomics landed: exact
+        assert torch.equal(rep.view(reps, 3, C).sum(0).cpu(), sums)
+        rep_host = rep.view(reps, 3, C).cpu()
+    ca = bn_check.bwd_coeffs(rep_host.numpy(), M, gammaA.numpy(), meanA.numpy(), invA.numpy(), 1)
+    _eq(dza, bn_check.backward(gm, _np(za), ca, _np(dadd) if use_dadd else None), "dza")
+    _eq(dg, ca["dgamma"], "dgammaA"), _eq(db, ca["dbeta"], "dbetaA"), _eq(a.shift, ca["shift"], "shiftA")
+    if use_zb:
+        cb = bn_check.bwd_coeffs(rep_host.numpy(), M, gammaB.numpy(), meanB.numpy(), invB.numpy(), 2)
+        _eq(dzb, bn_check.backward(gm, _np(zb), cb), "dzb")
+        _eq(dg2, cb["dgamma"], "dgammaB"), _eq(db2, cb["dbeta"], "dbetaB"), _eq(b.shift, cb["shift"], "shiftB")
+    if use_gout:
+        _eq(gout, gm, "gout")
+
+
+def test_bn_flat_and_chunked_grids_agree_bit_for_bit(gpu_device):
+    """The same 64 channels as a C = 64 tensor (flat grid) and embedded in a C = 256 tensor (chunked grid): forward
+    (two BN branches + ReLU) and backward (zb + dadd + y mask, presummed) give the same bits for those channels."""
+    dev, M, lo = gpu_device, 200, 64
+    g = torch.Generator(device="cpu").manual_seed(44)
+    outs = []
+    z_, t_, dy_, da_ = ((torch.randn(M, 256, generator=g) * 2).bfloat16() for _ in range(4))
+    par = [torch.rand(256, generator=g) + 0.5 for _ in range(6)] + [torch.randn(256, generator=g) * 0.2 for _ in range(6)]
+    sums = torch.randn(3, 256, generator=g).double() * 30
+    for C, sl in ((64, slice(lo, lo + 64)), (256, slice(0, 256))):
+        cut = lambda t: t[..., sl].contiguous().to(dev)
+        ga, gb, rva, rvb, gA2, gB2, ba, bb, rma, rmb, sha, shb = (cut(p) for p in par)
+        z, t, dy, da = cut(z_), cut(t_), cut(dy_), cut(da_)
+
+        def desc(zz, gamma, beta, rm, rv, sh):
+            d = zz.double() - sh.double()
+            st = conv.stats_buffer(C, dev)
+            st[3, 0], st[3, 1] = d.sum(0), (d * d).sum(0)
+            return cnn.bn_desc(st, gamma, beta, rm.clone(), rv.clone(), None, torch.empty(C, device=dev),
+                               torch.empty(C, device=dev), sh.clone())
+        A, B = desc(z, ga, ba, rma, rva, sha), desc(t, gb, bb, rmb, rvb, shb)
+        y, co = torch.empty(M, C, dtype=torch.bfloat16, device=dev), torch.empty(2, C, device=dev)
+        cnn.bn_apply(z, A, y, train=True, relu=True, z2=t, b=B, co_out=co)
+        reps = cnn.bn_bwd_chain_floats(C) // (3 * C)
+        rep = torch.zeros(reps, 3, C, dtype=torch.float64, device=dev)
+        rep[0] = cut(sums)
+        dg, db, dg2, db2 = (torch.empty(C, device=dev) for _ in range(4))
+        dza, dzb, gout = (torch.empty(M, C, dtype=torch.bfloat16, device=dev) for _ in range(3))
+        cnn.bn_bwd(dy, z, A, dg, db, dza, torch.zeros(3, C, dtype=torch.float64, device=dev), y=y, zb=t, b=B, dgamma_b=dg2,
+                   dbeta_b=db2, dzb=dzb, gout=gout, ws=rep.view(-1), dadd=da, chained=True, presummed=True)
+        torch.cuda.synchronize()
+        pick = (lambda v: v) if C == 64 else (lambda v: v[..., lo:lo + 64])
+        outs.append([pick(v).contiguous() for v in (y, co, A.smean, A.sinv, A.rmean, A.rvar, B.smean, B.sinv, dza, dzb, gout,
+                                                    dg, db, dg2, db2, A.shift, B.shift)])
+    assert float(outs[0][0].float().abs().max()) > 0
+    for i, (u, v) in enumerate(zip(*outs)):
+        assert torch.equal(u, v), i
+
+
+def test_bn_relu_mask_is_one_set_in_every_kernel_that_takes_it(gpu_device):
+    """A quarter of the rows at rounding distance from the ReLU threshold (sh = -fp32(z0 * sc)): the forward's y == 0
+    set, bn_bwd's masked set and the sets the reduce kernel, the dense DGRAD epilogue and the depthwise DGRAD epilogue
+    sum over are the same set -- the sign of the fused z * sc + sh.  Bit budget of the sums: the grad is a multiple of
+    1/8 <= 8 (dy: multiples of 1/4 <= 4, times a weight of 1/2, 1 or 2), z - mean a multiple of 1/8 <= 5, inv a power
+    of two <= 2, so a term is a multiple of 1/128 <= 80 and a sum over M = 256 rows stays below 2^15 * 128 = 2^22
+    quanta: every partial sum is exact in fp32 and the fp64 totals equal integer arithmetic in any order."""
+    dev = gpu_device
+    N, H, W, C = 16, 4, 4, 128
+    M = N * H * W
+    g = torch.Generator(device="cpu").manual_seed(8)
+    z = _dyadic((M, C), g, 0.125, 4.0)
+    z[z == 0] = 0.125
+    z[::4] = z[0]
+    z = z.bfloat16().to(dev)
+    gamma = (torch.rand(C, generator=g) + 0.5).to(dev)
+    rvar = (torch.rand(C, generator=g) + 0.5).to(dev)
+    rmean = torch.zeros(C, device=dev)             # eval mode, mean 0: sh = fma(-0, sc, beta) = beta exactly
+    co = torch.empty(2, C, device=dev)
+    y = torch.empty(M, C, dtype=torch.bfloat16, device=dev)
+    cnn.bn_apply(z, cnn.bn_desc(None, gamma, torch.zeros(C, device=dev), rmean, rvar), y, train=False, relu=True, co_out=co)
+    sc = co[0].clone()
+    sh = -(z[0].float() * sc)
+    cnn.bn_apply(z, cnn.bn_desc(None, gamma, sh, rmean, rvar), y, train=False, relu=True, co_out=co)
+    torch.cuda.synchronize()
+    assert torch.equal(co[0], sc) and torch.equal(co[1], sh)
+    exact = z.double() * sc.double() + sh.double()      # exact in fp64: 8-bit x 24-bit product, then one sum
+    mask = exact > 0
+    assert float((mask != ((z.float() * sc) + sh > 0)).float().mean()) > 0.05    # fused and unfused signs differ here
+    assert torch.equal(y.float() == 0, ~mask)                                     # the forward's ReLU
+    mean = _dyadic((C,), g, 0.125, 1.0).to(dev)
+    inv = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=g)].to(dev)
+    dy = _dyadic((N, H, W, C), g, 0.25, 4.0)
+    dy[dy == 0] = 0.25
+    dy = dy.bfloat16().to(dev)
+    msc = co.clone()
+    xhat = (z.double() - mean.double()) * inv.double()
+
+    def want(dx):
+        gm = torch.where(mask, dx.double().reshape(M, C), torch.zeros(M, C, dtype=torch.float64, device=dev))
+        return gm.sum(0), (gm * xhat).sum(0)
+
+    # bn_bwd: the reduce kernel's sums (atomics straight into red) and the apply kernel's masked set
+    a = cnn.bn_desc(gamma=gamma, smean=mean, sinv=inv)
+    dg, db = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    dz, gout = (torch.empty(M, C, dtype=torch.bfloat16, device=dev) for _ in range(2))
+    red = torch.zeros(3, C, dtype=torch.float64, device=dev)
+    cnn.bn_bwd(dy.view(M, C), z, a, dg, db, dz, red, gout=gout, mask_bn=msc)
+    torch.cuda.synchronize()
+    s0, s1 = want(dy)
+    assert torch.equal(red[0], s0) and torch.equal(red[1], s1)
+    assert torch.equal(gout.float() == 0, ~mask)
+    # dense DGRAD epilogue: 1x1 conv with the weight I / 2, so dx = dy / 2 exactly
+    w = (torch.eye(C) * 0.5).view(C, C, 1, 1).to(dev)
+    wd = torch.empty(conv.dgrad_image_numel(w.shape, C), dtype=torch.bfloat16, device=dev)
+    conv.dgrad_pack_weights([(w, wd, 1, 0, C)])
+    shp = ((N, H, W, C), C, 1, 1, 1, 0, C)
+    assert conv.dgrad_fusable(*shp)
+    wsp = torch.empty(max(conv.fd_ws_floats(*shp), 1), device=dev)
+    rep = torch.zeros(4, 3, C, dtype=torch.float64, device=dev)
+    bs = dict(rep=rep.view(-1), reps=4, z=z.view(N, H, W, C), y=None, mean=mean, inv=inv, msc=msc)
+    dx = conv.conv2d_dgrad(dy, conv.pack_weight(w), (N, H, W, C), 1, 0, ws=wsp, wd=wd, bn_sums=bs)
+    torch.cuda.synchronize()
+    assert torch.equal(dx.float(), dy.float() * 0.5)
+    s0, s1 = want(dx)
+    assert torch.equal(rep.sum(0)[0], s0) and torch.equal(rep.sum(0)[1], s1)
+    # depthwise DGRAD epilogue: only the centre tap is set (1/2, 1 or 2 by channel), so dx = dy * w exactly
+    wdw = torch.zeros(C, 1, 3, 3)
+    wdw[:, 0, 1, 1] = torch.tensor([0.5, 1.0, 2.0])[torch.arange(C) % 3]
+    wdw = wdw.to(dev)
+    rep.zero_()
+    dx = conv.dwconv_dgrad(dy, wdw, (N, H, W, C), 1, 1, bn_sums=bs)
+    torch.cuda.synchronize()
+    assert torch.equal(dx.float(), dy.float() * wdw[:, 0, 1, 1])
+    s0, s1 = want(dx)
+    assert torch.equal(rep.sum(0)[0], s0) and torch.equal(rep.sum(0)[1], s1)
