@@ -1629,8 +1629,11 @@ void launch_gconv(hipStream_t st, int mode, const ZTensor& x, const ZTensor& w, 
   };
   g.vec_x = vec_ok(x, Cg);
   g.vec_y = vec_ok(y, Og);
-  if (G <= 0 || O % G || x.size[1] != Cg * G || w.size[0] != O || g.R * g.S * GT > GC_LDS)
+  if (G <= 0 || O % G || x.size[1] != Cg * G || w.size[0] != O)
     throw std::invalid_argument("gconv: inconsistent shapes");
+  // the forward / dgrad kernels stage at least 8 channels of every tap per LDS chunk (cch = max(8, ...))
+  if ((long long)g.R * g.S * 8 * GT > GC_LDS)
+    throw std::invalid_argument("gconv: filter too large (R * S * 8 * GT floats must fit the LDS weight chunk)");
   if (mode == 0) {
     const long long n = y.size[0] * y.size[2] * y.size[3];
     if (n <= 0) return;

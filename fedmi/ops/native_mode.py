@@ -756,6 +756,15 @@ def _conv_kind(C, O, groups, k, stride, pad, dil):
     return "gconv"
 
 
+# the direct grouped conv stages at least 8 channels x GT = 8 outputs of every filter tap in its 8192-float LDS
+# weight chunk (zoo_ops.hip launch_gconv rejects anything larger): 11 x 11 fits, 12 x 12 does not
+_GCONV_MAX_TAPS = 8192 // (8 * 8)
+
+
+def _gconv_fits(k) -> bool:
+    return k[0] * k[1] <= _GCONV_MAX_TAPS
+
+
 def _pad_c(t: torch.Tensor, c8: int, cache: bool = False) -> torch.Tensor:
     """NHWC bf16 [.., C] (possibly a channel slice) -> contiguous [.., c8], zero channels C..c8.  ``cache``:
     reuse / keep the padded copy for the rest of the NativeMode block (a conv's input is padded by its
@@ -951,6 +960,8 @@ def _conv(func, input, weight, bias, stride, padding, dilation, transposed, outp
     N, C, H, W = input.shape
     O = weight.shape[0]
     kind = _conv_kind(C, O, groups, k, st, pd, dl)
+    if kind == "gconv" and (dl != (1, 1) or not _gconv_fits(k)):
+        return None     # nothing launched yet: a non-strict mode takes ATen, a strict mode reports the op
     dev = input.device
     w32 = weight if weight.dtype == torch.float32 else ew(torch.empty(weight.shape, device=dev), [weight], EW_COPY)
     if kind in ("mfma", "dw", "gdense", "dwpad"):
@@ -995,6 +1006,8 @@ def _conv_bwd(func, grad_output, input, weight, bias_sizes, stride, padding, dil
     N, C, H, W = input.shape
     O = weight.shape[0]
     kind = _conv_kind(C, O, groups, k, st, pd, dl)
+    if kind == "gconv" and (dl != (1, 1) or not _gconv_fits(k)):
+        return None     # as in _conv: before anything is launched
     dev = input.device
     w32 = weight if weight.dtype == torch.float32 else ew(torch.empty(weight.shape, device=dev), [weight], EW_COPY)
     gi = gw = gb = None
