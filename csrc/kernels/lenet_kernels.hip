@@ -842,59 +842,54 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
   bf16* w2c = reinterpret_cast<bf16*>(smem + S_O_W2C);
   bf16* w3s = reinterpret_cast<bf16*>(smem + S_O_W3);
   float bias1, bias2;
+  uint4 vl0, vl1;   // the late chunks, in named registers: an indexed two-element array went to scratch
+  // 16-B chunks: 720 image + 256 conv1-weight = 976, one per thread, are all conv1 needs and are stored to LDS
+  // in front of conv1's barrier.  The 832 dgrad-weight + 448 conv2-weight + 192 fc3 chunks (two per thread) go
+  // out in the same burst of requests, stay in registers across conv1 and are stored in front of conv2's
+  // barrier: conv1 starts when its own operands have landed, not when everything has.
+  constexpr int NWD = 16 * KDGP / 8, NW1 = 16 * K1C / 8, NW2 = 16 * K2C / 8, NW3 = 16 * 96 / 8;
+  constexpr int SL1 = NWD, SL2 = SL1 + NW2, SL3 = SL2 + NW3;
   {
-    // 720 image + 832 dgrad-weight + 256 conv1-weight + 448 conv2-weight + 192 fc3 16-B chunks (<= 3 per thread)
-    constexpr int NWD = 16 * KDGP / 8, NW1 = 16 * K1C / 8, NW2 = 16 * K2C / 8, NW3 = 16 * 96 / 8;
-    constexpr int NCH = 3;
-    constexpr int E1 = XP_CHUNKS, E2 = E1 + NWD, E3 = E2 + NW1, E4 = E3 + NW2, E5 = E4 + NW3;
-    static_assert(E5 <= NCH * NT_CONV, "stage: three chunks per thread");
+    constexpr int E1 = XP_CHUNKS, E2 = E1 + NW1;
+    static_assert(E2 <= NT_CONV, "stage: image + conv1 weights, one chunk per thread");
+    static_assert(SL3 <= 2 * NT_CONV, "stage: the late weights, two chunks per thread");
     static_assert(XP_ELEMS == 36 * 40 * 4 && (S_O_RED + S_R_XCL) % 16 == 0, "the prepared image is xcl, 16-B chunks");
-    uint4 v[NCH];
 #ifdef FEDMI_STAMPS
     const int dg = fedmi_ks1_diag;
     const size_t img_sample = (dg & 2) ? 0 : (size_t)s;
-    const int lim = (dg & 1) ? E1 : E5;
+    const bool wts = !(dg & 1);
 #else
     const size_t img_sample = (size_t)s;
-    constexpr int lim = E5;
+    constexpr bool wts = true;
 #endif
     // every load unconditional from a selected address: the segments do not end on wave boundaries, and with
     // one divergent branch per segment the stage took 5.6k cycles against 4.3k this way (the compiler split
-    // each 16-B load into four).  Chunks past E5 re-read a line of the image that is in use anyway and are not
-    // stored.  The kernel sits at the 128-VGPR cap: check for spills after any change here.
+    // each 16-B load into four).  Chunks past the last segment re-read a chunk that is in use anyway and are
+    // not stored.  The kernel sits at the 128-VGPR cap: check for spills after any change here.
     static_assert(PK_W2DG % 8 == 0 && PK_W1C % 8 == 0 && PK_W2C % 8 == 0 && PK_FC3 % 8 == 0, "16-B chunks");
     const uint4* xp4 = reinterpret_cast<const uint4*>(xprep + img_sample * XP_ELEMS);
     const uint4* pk4 = reinterpret_cast<const uint4*>(pk);
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-      const int e = tid + u * NT_CONV;
-      const int wo = e < E2 ? PK_W2DG / 8 + (e - E1) : e < E3 ? PK_W1C / 8 + (e - E2)
-                   : e < E4 ? PK_W2C / 8 + (e - E3) : PK_FC3 / 8 + (e - E4);
-      const uint4* src = (e >= E1 && e < lim) ? pk4 + wo : xp4 + min(e, E1 - 1);
-      v[u] = *src;
-    }
-    // the other global reads of the kernel's start go out in the same wave of requests (one
-    // memory latency for the whole stage instead of one per dependent group)
+    const uint4* ximg = xp4 + min(tid, E1 - 1);
+    const uint4 v0 = *((tid >= E1 && tid < E2 && wts) ? pk4 + PK_W1C / 8 + (tid - E1) : ximg);
+    FEDMI_STAMP(0, 7);                                 // first vector load issued
+    // the other global reads of the kernel's start go out in the same wave of requests (one memory latency
+    // for the whole stage instead of one per dependent group); the biases in front of the late chunks, whose
+    // return conv1's epilogue must not wait for (loads return in order)
     bias1 = n16 < C1 ? params[P_C1B + n16] : 0.f;
     bias2 = params[P_C2B + n16];
+    {
+      const int e1 = tid + NT_CONV;
+      const uint4* a0 = pk4 + (tid < SL1 ? PK_W2DG / 8 + tid : PK_W2C / 8 + (tid - SL1));
+      const uint4* a1 = pk4 + (e1 < SL2 ? PK_W2C / 8 + (e1 - SL1) : PK_FC3 / 8 + min(e1 - SL2, NW3 - 1));
+      vl0 = *(wts ? a0 : ximg);
+      vl1 = *(wts ? a1 : ximg);
+    }
     bwd_zero(L);
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-      const int e = tid + u * NT_CONV;
-      if (e < E1) {
-        reinterpret_cast<uint4*>(xcl)[e] = v[u];
-      } else if (e < E2) {
-        const int w = e - E1, row = w / (KDGP / 8), col = w - row * (KDGP / 8);
-        reinterpret_cast<uint4*>(wdg + row * BW_WDGS)[col] = v[u];
-      } else if (e < E3) {
-        const int w = e - E2, row = w / (K1C / 8), col = w - row * (K1C / 8);
-        reinterpret_cast<uint4*>(w1c + row * S_W1C_LD)[col] = v[u];
-      } else if (e < E4) {
-        const int w = e - E3, row = w / (K2C / 8), col = w - row * (K2C / 8);
-        reinterpret_cast<uint4*>(w2c + row * S_W2C_LD)[col] = v[u];
-      } else if (e < E5) {
-        reinterpret_cast<uint4*>(w3s)[e - E4] = v[u];
-      }
+    if (tid < E1) {
+      reinterpret_cast<uint4*>(xcl)[tid] = v0;
+    } else if (tid < E2) {
+      const int w = tid - E1, row = w / (K1C / 8), col = w - row * (K1C / 8);
+      reinterpret_cast<uint4*>(w1c + row * S_W1C_LD)[col] = v0;
     }
   }
   int go1[4];
@@ -903,7 +898,7 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
     const int g = ks * 4 + (lane >> 4);
     go1[ks] = g < 15 ? ((g / 3) * 40 + 2 * (g % 3)) * 4 : 0;
   }
-  __syncthreads();             // image and weights in LDS: conv1 starts here
+  __syncthreads();             // image and conv1 weights in LDS: conv1 starts here
   FEDMI_STAMP(1, 7);
   FEDMI_STAMP(0, 1);
   bf16x8 wb1[4];
@@ -966,6 +961,22 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
   bf16x8 w1r[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) w1r[m] = ld8(pk + PK_FC1 + (wave + 16 * m) * F0P + kc * 8);
+  // the stage's late chunks: conv2's and fc3's weight images and the dgrad weight image (rows of BW_WDGS)
+  {
+    auto store_late = [&](int e, const uint4& v) {
+      if (e < SL1) {
+        const int row = e / (KDGP / 8), col = e - row * (KDGP / 8);
+        reinterpret_cast<uint4*>(wdg + row * BW_WDGS)[col] = v;
+      } else if (e < SL2) {
+        const int w = e - SL1, row = w / (K2C / 8), col = w - row * (K2C / 8);
+        reinterpret_cast<uint4*>(w2c + row * S_W2C_LD)[col] = v;
+      } else if (e < SL3) {
+        reinterpret_cast<uint4*>(w3s)[e - SL2] = v;
+      }
+    };
+    store_late(tid, vl0);
+    store_late(tid + NT_CONV, vl1);
+  }
   __syncthreads();
   FEDMI_STAMP(0, 2);
   FEDMI_STAMP(0, 3);                                 // (pool1 is fused into conv1: empty phase)

@@ -56,6 +56,10 @@ def main():
         k0 = k0[k0[:, 0] > 0]
         if len(f) and len(k0):
             print(f"    stage loads landed med {np.median(k0[:len(f), 0] * 0 + f[:, 7] - k0[:len(f), 0]):8.0f}")
+            k0f = k0[:len(f)]
+            if (k0f[:, 7] > 0).all():       # start -> first vector load issued -> image + conv1 weights landed
+                print(f"    stage: start -> first load issued med {np.median(k0f[:, 7] - k0f[:, 0]):8.0f}  "
+                      f"issued -> landed med {np.median(f[:, 7] - k0f[:, 7]):8.0f}")
             fcn = ["fc1+h1T", "fc2", "fc3", "CE", "dH2", "dH1"]
             prev = k0[:len(f), 5]
             for j, nm in enumerate(fcn):
