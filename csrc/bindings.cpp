@@ -27,6 +27,8 @@ void read_stamps(unsigned long long*, bool);
 void set_ks1_diag(int);
 void launch_lenet_pack(hipStream_t, const float*, bf16*);
 void launch_lenet_prep_batch(hipStream_t, const uint8_t*, int, int, uint32_t, const int*, int, bf16*);
+int xlane_probe_helpers();
+void launch_lenet_xlane_probe(hipStream_t, const float*, const int*, int, float*);
 void launch_sgd_flat(hipStream_t, float*, const float*, float*, long, float, float, float, float, int, int);
 void launch_server_opt(hipStream_t, float*, float*, float*, float*, long, long, int, float, float, float, float);
 void launch_drift_grad(hipStream_t, int, float*, const float*, const float*, const float*, float*, float, long);
@@ -165,6 +167,13 @@ static void fedmi_bind(py::module_& m) {
     launch_lenet_pack(S(st), P<const float>(params), P<bf16>(pk));
     check_last("lenet_pack");
   });
+  // KS1's cross-lane helpers (kernels/xlane.h) next to the shuffle formulations they replaced, one wave per row
+  // of 64 floats: out is [rows][XLANE_PROBE_HELPERS][2 = helper, reference][64] floats, labels [rows] int32
+  m.attr("XLANE_PROBE_HELPERS") = xlane_probe_helpers();
+  m.def("lenet_xlane_probe", [](uintptr_t st, uintptr_t in, uintptr_t labels, int rows, uintptr_t out) {
+    launch_lenet_xlane_probe(S(st), P<const float>(in), P<const int>(labels), rows, P<float>(out));
+    check_last("lenet_xlane_probe");
+  }, py::arg("stream"), py::arg("inp"), py::arg("labels"), py::arg("rows"), py::arg("out"));
 
   // ---- flat-buffer ops --------------------------------------------------------
   m.def("sgd_flat", [](uintptr_t st, uintptr_t p, uintptr_t g, uintptr_t buf, long n, float lr, float mo, float wd,

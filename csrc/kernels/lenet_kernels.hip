@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "lenet_layout.h"
+#include "xlane.h"
 
 using namespace lenet;
 
@@ -567,7 +568,7 @@ FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int s
   const int kq = (lane >> 4) * 8, n16 = lane & 15, rq = (lane >> 4) * 4;
   float* db = L.db;
   // thread = (channel o, slot r < 32): the 25 positions of a channel sit in 32 consecutive lanes, so
-  // the conv2 bias grad is a shuffle reduction (400 LDS atomics onto 16 addresses took ~2k cycles)
+  // the conv2 bias grad is a cross-lane reduction (400 LDS atomics onto 16 addresses took ~2k cycles)
   if (tid < C2 * 32) {
     const int o = tid >> 5, rem = tid & 31;
     float g = 0.f;
@@ -580,8 +581,7 @@ FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int s
       L.dY2w[o * 160 + y * 16 + x] = gb;
       L.dY2c[((y + 4) * 18 + (x + 4)) * BW_DY2S + o] = gb;
     }
-#pragma unroll
-    for (int w = 1; w < 32; w <<= 1) g += __shfl_xor(g, w, 64);
+    g = xlane::sum32(g);
     if (rem == 0) db[o] = g;
   }
   __syncthreads();
@@ -661,8 +661,7 @@ FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int s
       }
     }
     // the 4 lane groups (rq) of a channel in a fixed xor order, then one write per (wave, channel)
-    csum += __shfl_xor(csum, 16, 64);
-    csum += __shfl_xor(csum, 32, 64);
+    csum = xlane::add_xor32(xlane::add_xor16(csum));
     if (n16 < C1 && lane < 16) db[16 + wave * C1 + n16] = csum;
     FEDMI_STAMP(sk, 7);    // wave 0: pool1 backward scatter done
   }
@@ -730,8 +729,8 @@ FEDMI_DEV void bwd_main(const BwdLds& L, float* __restrict__ slab, int sk, int s
 // (nothing waits on another workgroup, so a shared GPU can never deadlock it), no
 // restaging from global memory, one kernel boundary less than K12 -> K3.  The FC
 // layers of ONE sample are GEMVs: VALU dot products over 16-B weight chunks of the
-// packed images (L2-resident, read by all 128 workgroups) with 8-lane shuffle
-// reductions -- a 16-row MFMA tile would be 15/16 padding.
+// packed images (L2-resident, read by all 128 workgroups) with 8-lane DPP
+// reductions (xlane.h) -- a 16-row MFMA tile would be 15/16 padding.
 // KS1 writes the per-sample FC operands of the weight gradients (act2T, h1T, h2T,
 // dZ1T, dZ2T, dZ3T: sample-contiguous rows), the FC bias gradients and its loss.
 //
@@ -789,21 +788,28 @@ FEDMI_DEV float dot8f(const float* a, const bf16x8& b, float acc) {
   for (int j = 0; j < 8; ++j) acc += a[j] * (float)b[j];
   return acc;
 }
-FEDMI_DEV float sum8lanes(float v) {   // over the 8 consecutive lanes of a group
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  return v;
-}
 FEDMI_DEV float bfr(float v) { return (float)(bf16)v; }
-// sum over the 16 lanes of a DPP row (rotations: every lane of the row ends with the row total, each in a
-// fixed order -- deterministic)
-FEDMI_DEV float row_sum16(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));
-  return v;
+// fc1 forward of one thread: its k chunk x against the same chunk of its 8 weight rows, then the sums over the
+// 16 lanes of a DPP row -- one branch-free stream with the 8 rows' chains interleaved (as one guarded dot8 +
+// row sum per row it was eight serial 16-deep chains, each behind a branch).  Every lane computes: the chunk
+// index is clamped, so a lane past the last chunk (live == false) holds valid operands, and its zero goes in
+// with a select behind the in-lane sum.  Per row the arithmetic is dot8's and row_sum16's: the exact bf16 x bf16
+// products added one by one in element order from 0.f + p0 -- a product and an add each, by pragma, never an
+// FMA (the two differ when a product underflows) -- then the rotations 8, 4, 2, 1.
+FEDMI_DEV void fc1_rows(const bf16x8& x, const bf16x8 (&w)[8], bool live, float (&p)[8]) {
+#pragma clang fp contract(off)
+  float xf[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) xf[j] = (float)x[j];
+#pragma unroll
+  for (int m = 0; m < 8; ++m) p[m] = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int m = 0; m < 8; ++m) p[m] += xf[j] * (float)w[m][j];
+#pragma unroll
+  for (int m = 0; m < 8; ++m) p[m] = live ? p[m] : 0.f;
+  xlane::row_sum16(p);
 }
 
 __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
@@ -1040,11 +1046,11 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
   unsigned char* auxp = aux;
   float* fcb = reinterpret_cast<float*>(auxp + AUX_FCB) + (size_t)s * FCB_N;
   {
-    const bf16x8 xv = ld8(xrow + kc * 8);
+    float p[8];
+    fc1_rows(ld8(xrow + kc * 8), w1r, lane < KCH, p);
+    if ((lane & 15) == 0) {
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const float p = row_sum16(lane < KCH ? dot8(xv, w1r[m], 0.f) : 0.f);
-      if ((lane & 15) == 0) red[(wave + 16 * m) * 4 + (lane >> 4)] = p;
+      for (int m = 0; m < 8; ++m) red[(wave + 16 * m) * 4 + (lane >> 4)] = p[m];
     }
   }
   // backward weight chunks: fc2^T rows (dH1)
@@ -1066,7 +1072,7 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
     float acc = 0.f;
 #pragma unroll
     for (int i = 0; i < 2; ++i) acc = dot8f(fcs + SF_H1 + fq * 8 + 64 * i, w2v[i], acc);
-    acc = sum8lanes(acc);
+    acc = xlane::sum8(acc);
     if (fq == 0) {
       const float h = bfr(fn < F2 ? fmaxf(acc + fb2, 0.f) : 0.f);
       fcs[SF_H2 + fn] = h;
@@ -1081,13 +1087,13 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       if (fq * 8 + 64 * i < 96) acc = dot8f(fcs + SF_H2 + fq * 8 + 64 * i, ld8(w3s + fn * 96 + fq * 8 + 64 * i), acc);
-    acc = sum8lanes(acc);
+    acc = xlane::sum8(acc);
     if (fq == 0) fcs[SF_Z + fn] = fn < NCLS ? acc + fb3 : 0.f;
   }
   __syncthreads();
   FEDMI_STAMP(1, 2);
   // ---- cross-entropy (mean over the batch nb), accuracy, dZ3: lanes 0..15 of wave 0 hold one
-  //      class each (max / sum by xor shuffles)
+  //      class each (max / min / sum over the DPP row: xlane.h)
   if (wave == 0) {
     // the lane id passes through an empty asm so that n is recomputed here (one VALU op): KS1 sits at the
     // 128-VGPR cap, and n16 * 4 held from the kernel's start for this block was spilled to scratch -- a launch
@@ -1096,19 +1102,13 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
     asm volatile("" : "+v"(ln));
     const int n = ln & 15;
     const float zn = n < NCLS ? fcs[SF_Z + n] : -INFINITY;
-    float mx = zn;
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    const float mx = xlane::max16(zn);
     // first index reaching the max (torch argmax semantics)
-    float cand = (zn == mx) ? (float)n : 16.f;
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) cand = fminf(cand, __shfl_xor(cand, o, 64));
-    float se = n < NCLS ? __expf(zn - mx) : 0.f;
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) se += __shfl_xor(se, o, 64);
+    const float cand = xlane::min16((zn == mx) ? (float)n : 16.f);
+    const float se = xlane::sum16(n < NCLS ? __expf(zn - mx) : 0.f);
     const float lse = mx + __logf(se);
     const int y = label;
-    const float zy = __shfl(zn, y, 64);
+    const float zy = xlane::bcast(zn, y);   // the label is the same in every lane
     const float d = n < NCLS ? (__expf(zn - lse) - (n == y ? 1.f : 0.f)) * (1.f / (float)nb) : 0.f;
     if (lane < 16) {
       fcs[SF_DZ3 + n] = bfr(d);
@@ -1140,7 +1140,7 @@ __global__ __launch_bounds__(NT_CONV) void lenet_sample_step(
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       if (fq * 8 + 64 * i < 96) acc = dot8f(fcs + SF_DZ2 + fq * 8 + 64 * i, w2t[i], acc);
-    acc = sum8lanes(acc);
+    acc = xlane::sum8(acc);
     if (fq == 0) {
       const float g = (fn < F1 && fcs[SF_H1 + fn] > 0.f) ? acc : 0.f;
       fcs[SF_DZ1 + fn] = bfr(g);
@@ -1464,6 +1464,68 @@ __global__ __launch_bounds__(PREP_NT) void lenet_prep_batch(
 }
 
 // ---------------------------------------------------------------------------
+// lenet_xlane_probe: every helper of xlane.h that KS1 uses, next to the formulation it replaced (__shfl_xor /
+// __shfl butterflies; for fc1's row sums the separate mov_dpp + add), which lives on here only, as the
+// reference.  One wave per input row of 64 floats; out[row][helper][0 = helper, 1 = reference][lane].
+// tests/test_lenet_xlane_gpu.py compares the two as bit patterns.
+// ---------------------------------------------------------------------------
+constexpr int XLP_HELPERS = 8;   // sum8, sum16, max16, min16, sum32, add_xor16 + add_xor32, row_sum16, bcast
+__global__ __launch_bounds__(64) void lenet_xlane_probe(const float* __restrict__ in, const int* __restrict__ labels,
+                                                        int rows, float* __restrict__ out) {
+  const int r = blockIdx.x, lane = lane_id();
+  if (r >= rows) return;
+  const float v = in[(size_t)r * 64 + lane];
+  float* o = out + (size_t)r * XLP_HELPERS * 2 * 64 + lane;
+  auto put = [&](int h, float got, float ref) {
+    o[(2 * h) * 64] = got;
+    o[(2 * h + 1) * 64] = ref;
+  };
+  {   // sum8lanes of fc2 / fc3 / dH1
+    float s = v;
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    put(0, xlane::sum8(v), s);
+  }
+  {   // the cross-entropy block's three butterflies over 16 lanes
+    float s = v, mx = v, mn = v;
+#pragma unroll
+    for (int w = 1; w < 16; w <<= 1) s += __shfl_xor(s, w, 64);
+#pragma unroll
+    for (int w = 1; w < 16; w <<= 1) mx = fmaxf(mx, __shfl_xor(mx, w, 64));
+#pragma unroll
+    for (int w = 1; w < 16; w <<= 1) mn = fminf(mn, __shfl_xor(mn, w, 64));
+    put(1, xlane::sum16(v), s);
+    put(2, xlane::max16(v), mx);
+    put(3, xlane::min16(v), mn);
+  }
+  {   // the conv2 bias sum over 32 lanes
+    float s = v;
+#pragma unroll
+    for (int w = 1; w < 32; w <<= 1) s += __shfl_xor(s, w, 64);
+    put(4, xlane::sum32(v), s);
+  }
+  {   // csum of conv2 dgrad
+    float s = v;
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    put(5, xlane::add_xor32(xlane::add_xor16(v)), s);
+  }
+  {   // fc1's row sums: rotations 8, 4, 2, 1 (fc1_rows calls the same helper on its 8 rows at once)
+    float s = v;
+    s += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x128, 0xf, 0xf, false));
+    s += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x124, 0xf, 0xf, false));
+    s += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x122, 0xf, 0xf, false));
+    s += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x121, 0xf, 0xf, false));
+    put(6, xlane::row_sum16(v), s);
+  }
+  {   // the label lookup of the cross-entropy block
+    const int y = labels[r];
+    put(7, xlane::bcast(v, y), __shfl(v, y, 64));
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Host launchers (called by the native executor, csrc/runtime/lenet_engine.cpp)
 // ---------------------------------------------------------------------------
 namespace fedmi {
@@ -1566,6 +1628,15 @@ void launch_lenet_sample_step(hipStream_t st, const bf16* xprep, int nb, const b
   if (nb <= 0 || nb > MAX_TRAIN_BATCH) throw std::invalid_argument("lenet_sample_step: batch must be in [1, 128]");
   hipLaunchKernelGGL(lenet_sample_step, dim3(nb), dim3(NT_CONV), 0, st, xprep, nb, pk, params, labels, act2T, h1T,
                      reinterpret_cast<unsigned char*>(aux), dZ1T, conv_slab);
+}
+
+int xlane_probe_helpers() { return XLP_HELPERS; }
+
+// in: [rows][64] floats, labels: [rows] source lanes of the broadcast, out: [rows][helpers][2][64] floats
+void launch_lenet_xlane_probe(hipStream_t st, const float* in, const int* labels, int rows, float* out) {
+  if (rows <= 0 || rows > 65535) throw std::invalid_argument("lenet_xlane_probe: rows must be in [1, 65535]");
+  if (!in || !labels || !out) throw std::invalid_argument("lenet_xlane_probe: null buffer");
+  hipLaunchKernelGGL(lenet_xlane_probe, dim3(rows), dim3(64), 0, st, in, labels, rows, out);
 }
 
 // next_nb > 0: the launch also prepares the images of samples [next_base, next_base + next_nb) for the KS1
