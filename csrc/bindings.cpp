@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "kernels/common.h"
@@ -38,6 +39,10 @@ int dp_partials(long);
 void launch_dp(hipStream_t, float*, const float*, long, double*, double*, double, float, uint64_t, uint64_t, int);
 int robust_partials(long);
 void launch_robust_reduce(hipStream_t, const float*, long, int, long, int, float*, long long*, long long*);
+int geomed_partials(long);
+void launch_geomed_pass(hipStream_t, const float*, long, int, long, bool, const float*, const double*, double, float*,
+                        double*, double*, int);
+void launch_geomed(hipStream_t, const float*, long, int, long, int, double, float*, double*, double*);
 void launch_ef_delta(hipStream_t, const float*, const float*, const float*, float*, long);
 size_t topk_state_bytes();
 size_t topk_overflow_offset();
@@ -246,6 +251,52 @@ static void fedmi_bind(py::module_& m) {
     check_last("robust_reduce");
   }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("b_eff"), py::arg("out"),
      py::arg("partial"), py::arg("stats"));
+
+  // geometric-median aggregation (csrc/kernels/geomed.hip): out = the smoothed-Weiszfeld iterate after `iters`
+  // weighted passes over rows[0] .. rows[W-1] (ld floats apart), started from the mean of the finite entries.
+  // partial: geomed_partials(n) x 16 doubles of scratch; history: (iters + 1) x 3 x 16 doubles, row t = {sumsq, dist,
+  // w} of every rank after pass t (row iters - 1's w formed out, row iters' dist measures it).
+  m.def("geomed_partials", [](long n) {
+    if (n < 0) throw std::invalid_argument("geomed_partials: need n >= 0");
+    return geomed_partials(n);
+  });
+  auto geomed_check = [](const char* who, uintptr_t rows, long ld, int W, long n, double nu, uintptr_t out,
+                         uintptr_t partial, uintptr_t history) {
+    const std::string p = std::string(who) + ": ";
+    if (W < 2 || W > 16) throw std::invalid_argument(p + "W must be in 2..16");
+    if (n < 0) throw std::invalid_argument(p + "need n >= 0");
+    if (ld < n || ld % 4) throw std::invalid_argument(p + "the row stride ld must be >= n and a multiple of 4");
+    if (!(nu > 0.0) || !std::isfinite(nu)) throw std::invalid_argument(p + "need a finite nu > 0");
+    if (!rows || !out || !partial || !history) throw std::invalid_argument(p + "null buffer");
+    if ((rows | out) % 16) throw std::invalid_argument(p + "rows and out must be 16-byte aligned");
+    if ((partial | history) % 8) throw std::invalid_argument(p + "partial and history must be 8-byte aligned");
+    const uintptr_t row_bytes = ((uintptr_t)(W - 1) * (uintptr_t)ld + (uintptr_t)n) * 4, out_bytes = (uintptr_t)n * 4;
+    if (out < rows + row_bytes && rows < out + out_bytes) throw std::invalid_argument(p + "out must not alias rows");
+  };
+  m.def("geomed", [geomed_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, int iters, double nu,
+                                 uintptr_t out, uintptr_t partial, uintptr_t history) {
+    geomed_check("geomed", rows, ld, W, n, nu, out, partial, history);
+    if (iters < 1 || iters > 64) throw std::invalid_argument("geomed: iters must be in 1..64");
+    if (n == 0) return;
+    launch_geomed(S(st), P<const float>(rows), ld, W, n, iters, nu, P<float>(out), P<double>(partial),
+                  P<double>(history));
+    check_last("geomed");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("iters"), py::arg("nu"),
+     py::arg("out"), py::arg("partial"), py::arg("history"));
+  // one pass and its finish from caller-supplied fp32 weights (first: pass 0, the weights are not read and may be
+  // null); history_row: 3 x 16 doubles.  geomed is a loop over the same launcher.
+  m.def("geomed_pass", [geomed_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, bool first,
+                                      uintptr_t weights, uintptr_t out, uintptr_t partial, uintptr_t history_row,
+                                      double nu) {
+    geomed_check("geomed_pass", rows, ld, W, n, nu, out, partial, history_row);
+    if (!first && (!weights || weights % 4))
+      throw std::invalid_argument("geomed_pass: a weighted pass needs W fp32 weights, 4-byte aligned");
+    if (n == 0) return;
+    launch_geomed_pass(S(st), P<const float>(rows), ld, W, n, first, P<const float>(weights), nullptr, nu,
+                       P<float>(out), P<double>(partial), P<double>(history_row), 0);
+    check_last("geomed_pass");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("first"),
+     py::arg("weights"), py::arg("out"), py::arg("partial"), py::arg("history_row"), py::arg("nu") = 1e-6);
 
   // client-side drift correction of the flat gradient, between the backward pass and the SGD tail (kind: 0
   // fedprox -- g, p, anchor, mu; 1 scaffold -- g, corr, acc); the other kind's buffers may be 0

@@ -31,6 +31,7 @@ SOURCES = [
     CSRC / "kernels" / "client_opt.hip",
     CSRC / "kernels" / "dp.hip",
     CSRC / "kernels" / "robust.hip",
+    CSRC / "kernels" / "geomed.hip",
     CSRC / "kernels" / "compress.hip",
     CSRC / "kernels" / "conv_igemm.hip",
     CSRC / "kernels" / "cnn_ops.hip",
@@ -47,6 +48,10 @@ SOURCES = [
     CSRC / "bindings_io.cpp",
 ]
 HEADERS = sorted(CSRC.rglob("*.h"))
+
+# per-source flags.  geomed.hip names every fp32 rounding of its rule (__fadd_rn, __fmaf_rn, __fsub_rn): it is built
+# without packed fp32 instructions, so each of them is the scalar instruction the rule means.
+EXTRA_FLAGS = {"geomed.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 # build variants: the module name carries the variant (csrc/bindings.cpp FEDMI_MODULE); an A/B build adds
@@ -85,7 +90,7 @@ def _compile(src: Path, variant: str = "") -> Path:
     obj = bdir / (src.stem + ".o")
     cmd = [
         _hipcc(), "-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", *VARIANTS[variant],
-        "-Wno-unused-result", "-I", str(CSRC),
+        *EXTRA_FLAGS.get(src.name, []), "-Wno-unused-result", "-I", str(CSRC),
         "-I", pybind11.get_include(), "-I", sysconfig.get_paths()["include"],
         "-c", str(src), "-o", str(obj),
     ]

@@ -198,13 +198,19 @@ class RobustAgg(ReplicatedState):
 
 
 def add_robust_flags(ap) -> None:
-    """``--robust`` and ``--robust-trim`` (fedmi.cli.client, tools/fedavg_sim.py)."""
-    ap.add_argument("--robust", default="none", choices=["none", *KINDS],
+    """``--robust``, ``--robust-trim``, ``--robust-iters`` and ``--robust-nu`` (fedmi.cli.client,
+    tools/fedavg_sim.py)."""
+    ap.add_argument("--robust", default="none", choices=["none", *KINDS, "geomed"],
                     help="Byzantine-robust aggregation (fedmi.parallel.robust): the coordinate-wise median or trimmed "
-                         "mean of the clients' models replaces the plain mean; every client must pass the same settings")
+                         "mean of the clients' models replaces the plain mean; every client must pass the same settings."
+                         "  geomed (fedmi.parallel.geomed): the geometric median of the clients' whole models")
     ap.add_argument("--robust-trim", type=int, default=1, metavar="B",
                     help="trimmed: cut the B smallest and the B largest values of every coordinate (at most "
                          "(clients - 1) // 2 are cut: a shrinking federation degrades towards the median)")
+    ap.add_argument("--robust-iters", type=int, default=8, metavar="T",
+                    help="geomed: weighted Weiszfeld passes after the starting mean (1..64)")
+    ap.add_argument("--robust-nu", type=float, default=1e-6, metavar="NU",
+                    help="geomed: the floor of a client's distance in its weight 1 / max(NU, distance)")
 
 
 def check_robust_flags(a, error) -> None:
@@ -213,6 +219,10 @@ def check_robust_flags(a, error) -> None:
         return
     if a.robust_trim < 1:
         error("--robust-trim must be >= 1 (the number of values cut on either side of every coordinate)")
+    if not 1 <= getattr(a, "robust_iters", 8) <= 64:
+        error("--robust-iters must lie in 1..64 (the weighted passes of the geometric median)")
+    if not getattr(a, "robust_nu", 1e-6) > 0:
+        error("--robust-nu must be > 0 (the smoothing floor of a client's distance)")
     if getattr(a, "agg", "collective") == "grpc":
         error("--robust needs --agg collective: with --agg grpc the coordinator averages the clients' models "
               "(reference peers), nothing folds them robustly")
@@ -228,8 +238,12 @@ def check_robust_flags(a, error) -> None:
               "statistic of individually noised updates is not a post-processing of the sum (--dp-clip alone is fine)")
 
 
-def make_robust(kind: Optional[str], trainer=None, trim: int = 1) -> Optional[RobustAgg]:
-    """None for ``none`` (nothing new is launched)."""
+def make_robust(kind: Optional[str], trainer=None, trim: int = 1, iters: int = 8, nu: float = 1e-6):
+    """None for ``none`` (nothing new is launched); a :class:`fedmi.parallel.geomed.GeoMedAgg` for ``geomed``."""
     if kind in (None, "", "none"):
         return None
+    if kind == "geomed":
+        from .geomed import GeoMedAgg, GeoMedConfig
+
+        return GeoMedAgg(trainer, GeoMedConfig(kind, iters, nu))
     return RobustAgg(trainer, RobustConfig(kind, trim))

@@ -48,6 +48,8 @@ def robust_stack(robust, states, nat=None):
     from fedmi.parallel.robust import robust_reduce_torch
 
     W, n = len(states), states[0].numel()
+    if robust.cfg.kind == "geomed":
+        return geomed_stack(robust, states, nat)
     b = robust.cfg.b_eff(W)
     if not states[0].is_cuda:
         return robust_reduce_torch(torch.stack(states), b)
@@ -63,6 +65,29 @@ def robust_stack(robust, states, nat=None):
     nat.robust_reduce(native.stream_handle(dev), rows.data_ptr(), ld, W, n, b, out.data_ptr(), partial.data_ptr(),
                       stats.data_ptr())
     return out, stats[:W]
+
+
+def geomed_stack(robust, states, nat=None):
+    """The geometric-median aggregate of the simulated clients' float states and its history ``[T + 1, 3, W]``
+    (sumsq, dist, w per pass): ``geomed`` (csrc/kernels/geomed.hip) on a GPU, its torch twin elsewhere."""
+    from fedmi import native
+    from fedmi.parallel.geomed import geomed_torch
+
+    W, n, T = len(states), states[0].numel(), robust.cfg.iters
+    if not states[0].is_cuda:
+        return geomed_torch(torch.stack(states), T, robust.cfg.nu)
+    nat = nat or native.require()
+    dev = states[0].device
+    ld = (n + 3) & ~3
+    rows = torch.zeros((W, ld), dtype=torch.float32, device=dev)
+    for r, x in enumerate(states):
+        rows[r, :n].copy_(x)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    partial = torch.zeros((max(1, nat.geomed_partials(n)), 16), dtype=torch.float64, device=dev)
+    history = torch.zeros((T + 1, 3, 16), dtype=torch.float64, device=dev)
+    nat.geomed(native.stream_handle(dev), rows.data_ptr(), ld, W, n, T, robust.cfg.nu, out.data_ptr(),
+               partial.data_ptr(), history.data_ptr())
+    return out, history[:, :, :W]
 
 
 def _eval_batch_bn(tr) -> None:
@@ -125,7 +150,7 @@ def _run_seed(a, seed, data, dev, out) -> None:
     # one DP guard per simulated client: its own key, anchor and draw counter; each adds its 1/sqrt(W) noise share
     dps = [make_dp(a.dp_clip, tr, a.dp_noise, a.dp_delta, a.dp_seed, who=f"seed{seed}/client{r}")
            for r, tr in enumerate(clients)]
-    robust = make_robust(a.robust, clients[0], a.robust_trim)
+    robust = make_robust(a.robust, clients[0], a.robust_trim, a.robust_iters, a.robust_nu)
     for rnd in range(1, a.rounds + 1):
         t0 = time.perf_counter()
         tstats = []
@@ -189,7 +214,13 @@ def _run_seed(a, seed, data, dev, out) -> None:
             rec.update(dp_clip=a.dp_clip, dp_noise=a.dp_noise, dp_delta=a.dp_delta, dp_epsilon=rows[0]["dp_epsilon"],
                        dp_norm=[round(r.get("dp_norm", -1.0), 4) for r in rows],
                        dp_scale=[round(r.get("dp_scale", -1.0), 4) for r in rows])
-        if robust is not None:
+        if robust is not None and a.robust == "geomed":
+            # cut is the history here: the weights that formed the aggregate, the distances to it
+            T = robust.cfg.iters
+            rec.update(robust_kind=a.robust, robust_iters=T,
+                       robust_weight=cut[T - 1, 2].tolist() if cut is not None else None,
+                       robust_dist=cut[T, 1].tolist() if cut is not None else None)
+        elif robust is not None:
             rec.update(robust_kind=a.robust, robust_trim=robust.cfg.b_eff(W),
                        robust_cut=cut.tolist() if cut is not None else None)
         if a.attack != "none":
