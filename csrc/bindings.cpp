@@ -236,15 +236,24 @@ static void fedmi_bind(py::module_& m) {
     if (n < 0) throw std::invalid_argument("robust_partials: need n >= 0");
     return robust_partials(n);
   });
-  m.def("robust_reduce", [](uintptr_t st, uintptr_t rows, long ld, int W, long n, int b_eff, uintptr_t out,
-                            uintptr_t partial, uintptr_t stats) {
-    if (W < 2 || W > 16) throw std::invalid_argument("robust_reduce: W must be in 2..16");
+  // the contract the gathered-rows kernels share: W rows of ld floats, n used; `last` is the 8-byte-aligned buffer after
+  // partial (stats or history)
+  auto rows_check = [](const char* who, uintptr_t rows, long ld, int W, long n, uintptr_t out, uintptr_t partial,
+                       uintptr_t last) {
+    const std::string p = std::string(who) + ": ";
+    if (W < 2 || W > 16) throw std::invalid_argument(p + "W must be in 2..16");
+    if (n < 0) throw std::invalid_argument(p + "need n >= 0");
+    if (ld < n || ld % 4) throw std::invalid_argument(p + "the row stride ld must be >= n and a multiple of 4");
+    if (!rows || !out || !partial || !last) throw std::invalid_argument(p + "null buffer");
+    if ((rows | out) % 16) throw std::invalid_argument(p + "rows and out must be 16-byte aligned");
+    if ((partial | last) % 8) throw std::invalid_argument(p + "partial and stats / history must be 8-byte aligned");
+    const uintptr_t row_bytes = ((uintptr_t)(W - 1) * (uintptr_t)ld + (uintptr_t)n) * 4, out_bytes = (uintptr_t)n * 4;
+    if (out < rows + row_bytes && rows < out + out_bytes) throw std::invalid_argument(p + "out must not alias rows");
+  };
+  m.def("robust_reduce", [rows_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, int b_eff, uintptr_t out,
+                                      uintptr_t partial, uintptr_t stats) {
+    rows_check("robust_reduce", rows, ld, W, n, out, partial, stats);
     if (b_eff < 0 || b_eff > (W - 1) / 2) throw std::invalid_argument("robust_reduce: need 0 <= b_eff <= (W - 1) / 2");
-    if (n < 0) throw std::invalid_argument("robust_reduce: need n >= 0");
-    if (ld < n || ld % 4) throw std::invalid_argument("robust_reduce: the row stride ld must be >= n and a multiple of 4");
-    if (!rows || !out || !partial || !stats) throw std::invalid_argument("robust_reduce: null buffer");
-    if ((rows | out) % 16) throw std::invalid_argument("robust_reduce: rows and out must be 16-byte aligned");
-    if ((partial | stats) % 8) throw std::invalid_argument("robust_reduce: partial and stats must be 8-byte aligned");
     if (n == 0) return;
     launch_robust_reduce(S(st), P<const float>(rows), ld, W, n, b_eff, P<float>(out), P<long long>(partial),
                          P<long long>(stats));
@@ -260,18 +269,10 @@ static void fedmi_bind(py::module_& m) {
     if (n < 0) throw std::invalid_argument("geomed_partials: need n >= 0");
     return geomed_partials(n);
   });
-  auto geomed_check = [](const char* who, uintptr_t rows, long ld, int W, long n, double nu, uintptr_t out,
-                         uintptr_t partial, uintptr_t history) {
-    const std::string p = std::string(who) + ": ";
-    if (W < 2 || W > 16) throw std::invalid_argument(p + "W must be in 2..16");
-    if (n < 0) throw std::invalid_argument(p + "need n >= 0");
-    if (ld < n || ld % 4) throw std::invalid_argument(p + "the row stride ld must be >= n and a multiple of 4");
-    if (!(nu > 0.0) || !std::isfinite(nu)) throw std::invalid_argument(p + "need a finite nu > 0");
-    if (!rows || !out || !partial || !history) throw std::invalid_argument(p + "null buffer");
-    if ((rows | out) % 16) throw std::invalid_argument(p + "rows and out must be 16-byte aligned");
-    if ((partial | history) % 8) throw std::invalid_argument(p + "partial and history must be 8-byte aligned");
-    const uintptr_t row_bytes = ((uintptr_t)(W - 1) * (uintptr_t)ld + (uintptr_t)n) * 4, out_bytes = (uintptr_t)n * 4;
-    if (out < rows + row_bytes && rows < out + out_bytes) throw std::invalid_argument(p + "out must not alias rows");
+  auto geomed_check = [rows_check](const char* who, uintptr_t rows, long ld, int W, long n, double nu, uintptr_t out,
+                                   uintptr_t partial, uintptr_t history) {
+    rows_check(who, rows, ld, W, n, out, partial, history);
+    if (!(nu > 0.0) || !std::isfinite(nu)) throw std::invalid_argument(std::string(who) + ": need a finite nu > 0");
   };
   m.def("geomed", [geomed_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, int iters, double nu,
                                  uintptr_t out, uintptr_t partial, uintptr_t history) {

@@ -28,6 +28,7 @@
 #include "peer_comm.h"
 
 #include "kernels/robust_fold.h"
+#include "kernels/row_sweep.h"
 
 #include <algorithm>
 #include <cstring>
@@ -150,6 +151,14 @@ __global__ __launch_bounds__(256) void peer_oneshot_f32_kernel(PeerArgs a, const
 // (key, rank), so every rank computes the same bits.  Same staging slot, barrier and call counter as every other
 // collective of the communicator.  partial[block][r] = the block's count of coordinates at which rank r was cut
 // (a block whose barrier failed writes nothing: the communicator's error word is set, the round is void).
+// Prologue: stage-in and barrier; then the row sweep of kernels/row_sweep.h over the peers' staged rows (the n % 4
+// tail falls to lanes t < n % 4 of block 0); epilogue: the block's cut counts.
+struct PeerRows {
+  const PeerArgs& a;
+  int slot;
+  PDEV float* operator()(int p) const { return reinterpret_cast<float*>(region(a, p, slot, 0)); }
+};
+
 template <int W>
 __global__ __launch_bounds__(256) void peer_robust_f32_kernel(PeerArgs a, const float* in, float* out, long long n,
                                                               int trim, long long* partial) {
@@ -158,37 +167,15 @@ __global__ __launch_bounds__(256) void peer_robust_f32_kernel(PeerArgs a, const 
   const int slot = ep & 1;
   const long long n4 = n >> 2, stride = (long long)gridDim.x * 256;
   const int tail = (int)(n & 3);
-  float* mine = reinterpret_cast<float*>(region(a, a.rank, slot, 0));
+  const PeerRows staged{a, slot};
+  float* mine = staged(a.rank);
   for (long long i = (long long)b * 256 + t; i < n4; i += stride)
-    reinterpret_cast<float4*>(mine)[i] = reinterpret_cast<const float4*>(in)[i];
+    fedmi::flat_store<4>(mine, i << 2, fedmi::flat_load<4>(in, i << 2));
   if (b == 0 && t < tail) mine[n4 * 4 + t] = in[n4 * 4 + t];
   if (!peer_barrier(a, 0, b, ep)) return;
-  fedmi::RobustCuts<W> cuts;
-  for (long long i = (long long)b * 256 + t; i < n4; i += stride) {
-    float4 v[W];
-#pragma unroll
-    for (int p = 0; p < W; ++p) v[p] = reinterpret_cast<const float4*>(region(a, p, slot, 0))[i];
-    float o[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float x[W];
-#pragma unroll
-      for (int p = 0; p < W; ++p) x[p] = reinterpret_cast<const float*>(&v[p])[c];
-      uint32_t cut;
-      o[c] = fedmi::robust_fold<W>(x, trim, cut);
-      cuts.add(cut);
-    }
-    reinterpret_cast<float4*>(out)[i] = make_float4(o[0], o[1], o[2], o[3]);
-  }
-  if (b == 0 && t < tail) {
-    float x[W];
-#pragma unroll
-    for (int p = 0; p < W; ++p) x[p] = reinterpret_cast<const float*>(region(a, p, slot, 0))[n4 * 4 + t];
-    uint32_t cut;
-    out[n4 * 4 + t] = fedmi::robust_fold<W>(x, trim, cut);
-    cuts.add(cut);
-  }
-  cuts.store(partial + (long long)b * fedmi::kRobustMaxRanks);
+  fedmi::RobustRule<W> rule{trim};
+  fedmi::row_sweep<W>(staged, n, out, rule);
+  rule.cuts.store(partial + (long long)b * fedmi::kRobustMaxRanks);
   end_call(a, b, ep);
 }
 

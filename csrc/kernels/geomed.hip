@@ -9,21 +9,23 @@
 // A round is pass 0 (FIRST) and T weighted passes, each followed by its finish: 2 (T + 1) launches on one stream, no
 // host sync in between; pass t reads the weights that finish t - 1 wrote.  The result is the z of pass T.
 //
-// One pass reads every row exactly once and never reads z back: a lane takes one float4 per row (W independent 16-B
-// loads in flight), forms the four z, stores them with one 16-B store and then accumulates the W x 4 squared
-// distances from the values still in registers: (W + 1) * 4 B of traffic per coordinate.  The n % 4 entries after the
-// whole vectors go through the same per-coordinate function.  Registers at W = 16: 64 of rows, 32 of fp64
+// One pass reads every row exactly once and never reads z back: it is the row sweep of row_sweep.h with GeomedRule --
+// a lane takes one float4 per row, forms the four z (coord), stores them with one 16-B store and then accumulates the
+// W x 4 squared distances from the values still in registers (stored): (W + 1) * 4 B of traffic per coordinate.  The
+// n % 4 entries after the whole vectors go through the same two calls.  Registers at W = 16: 64 of rows, 32 of fp64
 // accumulators, 4 of z; the weights are wave-uniform and live in SGPRs.
 //
 // Determinism.  (x - z) is an fp32 number, so its square is exact in fp64 and the sums' only roundings are their
 // additions, in a fixed order: a lane adds its grid-strided coordinates in index order; the workgroup folds its 256
 // lanes per rank in a two-level 16-ary LDS tree (lane (r, j) adds the 16 entries j, j + 16, .. of rank r in that order,
-// lane (r, 0) the 16 results); the finish folds the partials in 64 strided groups and an LDS tree.  The grid is a
+// lane (r, 0) the 16 results); the finish folds the partials in 64 strided groups and an LDS tree (fold_partial_rows,
+// robust_fold.h; tests/geomed_check.py emulates the whole order and the GPU test compares bits).  The grid is a
 // function of n alone (flat_grid) and there are no atomics: the same rows give the same bits on every run and client.
 #include <math.h>
 
 #include "flat_map.h"
 #include "robust_fold.h"
+#include "row_sweep.h"
 
 namespace {
 
@@ -66,53 +68,31 @@ FEDMI_DEV void geomed_acc(const float (&x)[W], float z, double (&acc)[W]) {
   }
 }
 
-// (no __restrict__ and `unroll 1` on the trips, as in robust_reduce_kernel: otherwise the next trip's W loads are
-// hoisted over the accumulation and the kernel spills)
+// The rule of one pass for row_sweep.h: z before the store, the fp64 sums after it, per rank in index order.
+template <int W, bool FIRST>
+struct GeomedRule {
+  float w[W];
+  double acc[W];
+  FEDMI_DEV float coord(const float (&x)[W]) const { return geomed_z<W, FIRST>(x, w); }
+  FEDMI_DEV void stored(const float (&x)[W], float z) { geomed_acc<W>(x, z, acc); }
+};
+
 template <int W, bool FIRST>
 __global__ __launch_bounds__(GM_THREADS) void geomed_pass_kernel(const float* rows, long ld, long n, const float* w32,
                                                                  const double* w64, float* out, double* partial) {
   __shared__ double sh[W][GM_THREADS];
-  float w[W];
+  GeomedRule<W, FIRST> rule;
 #pragma unroll
   for (int r = 0; r < W; ++r) {                     // once per kernel, the same in every lane: scalar registers
     float v = 0.f;
     if (!FIRST) v = w32 ? w32[r] : (float)w64[r];
-    w[r] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+    rule.w[r] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+    rule.acc[r] = 0.0;
   }
-  double acc[W];
-#pragma unroll
-  for (int r = 0; r < W; ++r) acc[r] = 0.0;
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-#pragma unroll 1
-  for (long i = t; i < n4; i += stride) {
-    FlatVec<4> v[W], o;
-#pragma unroll
-    for (int r = 0; r < W; ++r) v[r] = flat_load<4>(rows + r * ld, i << 2);
-    float x[4][W];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-#pragma unroll
-      for (int r = 0; r < W; ++r) x[c][r] = v[r][c];
-      o[c] = geomed_z<W, FIRST>(x[c], w);
-    }
-    flat_store<4>(out, i << 2, o);                  // z leaves before the fp64 work and is never read back
-#pragma unroll
-    for (int c = 0; c < 4; ++c) geomed_acc<W>(x[c], o[c], acc);   // per rank c ascending: index order
-  }
-#pragma unroll 1
-  for (long i = (n4 << 2) + t; i < n; i += stride) {   // tail (n % 4 entries)
-    float x[W];
-#pragma unroll
-    for (int r = 0; r < W; ++r) x[r] = rows[r * ld + i];
-    const float z = geomed_z<W, FIRST>(x, w);
-    out[i] = z;
-    geomed_acc<W>(x, z, acc);
-  }
+  row_sweep<W>(StridedRows{rows, ld}, n, out, rule);   // z leaves before the fp64 work and is never read back
   // the workgroup's sum per rank: 256 lanes -> 16 -> 1, each level 16 additions in a fixed order
 #pragma unroll
-  for (int r = 0; r < W; ++r) sh[r][threadIdx.x] = acc[r];
+  for (int r = 0; r < W; ++r) sh[r][threadIdx.x] = rule.acc[r];
   __syncthreads();
   const int r = threadIdx.x / GM_FAN, j = threadIdx.x % GM_FAN;
   if (r < W) {
@@ -130,29 +110,15 @@ __global__ __launch_bounds__(GM_THREADS) void geomed_pass_kernel(const float* ro
   }
 }
 
-// one workgroup of 1024, as robust_finish_kernel: lane (g, r) adds rank r's partials g, g + 64, .. in that order, an
-// LDS tree folds the 64 groups, lanes r < W form the weights
-constexpr int GF_THREADS = 1024;
-
-__global__ __launch_bounds__(GF_THREADS) void geomed_finish_kernel(const double* partial, int n_partial, int W,
-                                                                   double nu, int t, double* history) {
-  __shared__ double sh[GF_THREADS];
+// fold_partial_rows on fp64 (its order is part of the rule's bits), then lanes r < W form the weights
+__global__ __launch_bounds__(kFoldThreads) void geomed_finish_kernel(const double* partial, int n_partial, int W,
+                                                                     double nu, int t, double* history) {
   __shared__ double beta[kRobustMaxRanks];
-  const int r = threadIdx.x & (kRobustMaxRanks - 1), g = threadIdx.x / kRobustMaxRanks;
-  double acc = 0.0;
-  if (r < W)
-    for (int i = g; i < n_partial; i += GF_THREADS / kRobustMaxRanks) acc += partial[(long)i * kRobustMaxRanks + r];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-#pragma unroll
-  for (int s = GF_THREADS / 2; s >= kRobustMaxRanks; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
+  const double sum = fold_partial_rows(partial, n_partial, W);
   const bool mine = (int)threadIdx.x < W;
   double sumsq = 0.0, dist = 0.0;
   if (mine) {
-    sumsq = sh[threadIdx.x];
+    sumsq = sum;
     dist = __dsqrt_rn(sumsq);
     beta[threadIdx.x] = isfinite(dist) ? __ddiv_rn(1.0, fmax(nu, dist)) : 0.0;
   }
@@ -191,7 +157,7 @@ void launch_geomed_pass(hipStream_t st, const float* rows, long ld, int W, long 
       hipLaunchKernelGGL((geomed_pass_kernel<kW, false>), dim3(grid), dim3(GM_THREADS), 0, st, rows, ld, n, w32, w64,
                          out, partial);
   });
-  hipLaunchKernelGGL(geomed_finish_kernel, dim3(1), dim3(GF_THREADS), 0, st, partial, grid, W, nu, t, history);
+  hipLaunchKernelGGL(geomed_finish_kernel, dim3(1), dim3(kFoldThreads), 0, st, partial, grid, W, nu, t, history);
 }
 
 // rows: W rows of ld floats, 16-byte aligned, ld % 4 == 0, ld >= n; out: n floats, 16-byte aligned, not aliasing rows;

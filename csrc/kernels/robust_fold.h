@@ -1,5 +1,6 @@
-// fedmi — the coordinate-wise robust fold (median / trimmed mean over the clients' values of one coordinate), shared by
-// robust_reduce (robust.hip) and peer_robust_f32_kernel (comm/peer_comm.hip).  Rule: fedmi/parallel/robust.py.
+// fedmi — the coordinate-wise robust fold (median / trimmed mean over the clients' values of one coordinate): RobustRule
+// is the rule that robust_reduce (robust.hip) and peer_robust_f32_kernel (comm/peer_comm.hip) hand to the row sweep
+// (row_sweep.h).  Rule: fedmi/parallel/robust.py.  Also here: fold_partial_rows, the finish kernels' column sums.
 //
 // One call takes the W values x_0 .. x_{W-1} of one coordinate (rank order, in registers) and the trim count b:
 //   key_r   = 0xFFFFFFFF if x_r is NaN;  bits ^ 0xFFFFFFFF if the sign bit is set;  bits ^ 0x80000000 otherwise
@@ -145,6 +146,46 @@ struct RobustCuts {
     if (threadIdx.x < kRobustMaxRanks) row[threadIdx.x] = (long long)sh[threadIdx.x];
   }
 };
+
+// The fold as a rule of row_sweep.h, counting the cuts as it goes; the epilogue is cuts.store.
+template <int W>
+struct RobustRule {
+  int b;
+  RobustCuts<W> cuts;
+  FEDMI_DEV float coord(const float (&x)[W]) {
+    uint32_t cut;
+    const float v = robust_fold<W>(x, b, cut);
+    cuts.add(cut);
+    return v;
+  }
+  FEDMI_DEV void stored(const float (&)[W], float) {}
+};
+
+// One workgroup of kFoldThreads folds n_partial rows of kRobustMaxRanks T (one row per workgroup of a sweep) and
+// returns, in every lane, the sum of column r = threadIdx.x % 16 -- 0 for r >= W.  The order is fixed: lane (g, r),
+// g = threadIdx.x / 16, adds rows g, g + 64, .. in that order from 0, then a binary LDS tree folds the 64 groups
+// (slot += slot + s for s = 512 .. 16).  1024 lanes: the 2048 partial rows of a large state are 32
+// dependent-latency trips per lane, not 128.
+constexpr int kFoldThreads = 1024;
+
+template <class T>
+FEDMI_DEV T fold_partial_rows(const T* partial, int n_partial, int W) {
+  __shared__ T sh[kFoldThreads];
+  const int r = threadIdx.x & (kRobustMaxRanks - 1), g = threadIdx.x / kRobustMaxRanks;
+  T acc = 0;
+  if (r < W) {
+#pragma unroll 4
+    for (int i = g; i < n_partial; i += kFoldThreads / kRobustMaxRanks) acc += partial[(long)i * kRobustMaxRanks + r];
+  }
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = kFoldThreads / 2; s >= kRobustMaxRanks; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[r];
+}
 
 // Calls f(std::integral_constant<int, W>{}) for the run-time W in 2 .. 16; false for any other W.
 template <class F, int W = 2>

@@ -42,7 +42,7 @@ import torch
 
 from .. import native
 from .client_opt import fma32
-from .replicated import ReplicatedConfig, ReplicatedState
+from .replicated import HostMirror, ReplicatedConfig, ReplicatedState
 
 KINDS = ("clip", "gaussian")
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -175,11 +175,10 @@ class DpGuard(ReplicatedState):
         self.draw = 0
         self.anchor = x[:self.k].detach().clone()
         self.stats = torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=torch.float64, device=self.dev)
-        self._partial = self._host = self._copied = None
+        self._mirror = HostMirror(self.stats)
+        self._partial = None
         if self._nat is not None:
             self._partial = torch.zeros(max(1, self._nat.dp_partials(self.k)), dtype=torch.float64, device=self.dev)
-            self._host = torch.zeros(4, dtype=torch.float64).pin_memory()
-            self._copied = torch.cuda.Event()
         self._seen = None                # (norm, scale) of the newest stats row known on the host
 
     def _rolled(self) -> List[torch.Tensor]:
@@ -198,9 +197,7 @@ class DpGuard(ReplicatedState):
             self._nat.dp_privatize(native.stream_handle(self.dev), x.data_ptr(), self.anchor.data_ptr(), self.n,
                                    self.k, self._partial.data_ptr(), self.stats.data_ptr(), c.clip, c.noise,
                                    int(world), self.key, draw)
-            # the row reaches the host behind the launches; read at the next round's start (round_stats)
-            self._host.copy_(self.stats, non_blocking=True)
-            self._copied.record(torch.cuda.current_stream(self.dev))
+            self._mirror.post()
             return
         with torch.no_grad():
             k = self.k
@@ -214,16 +211,13 @@ class DpGuard(ReplicatedState):
                 g = gaussian(self.key, draw, k, torch.float32).to(x.device)
                 x[:k] = fma32(sigma32(c.clip, c.noise, world), g, x[:k])
             self.stats.copy_(torch.tensor([sumsq, norm, scale, 0.0], dtype=torch.float64))
+        self._mirror.post()
 
     def _collect(self) -> None:
-        """Pick up the last call's stats row if it has reached the host.  Never waits: a row still in flight is
-        picked up by a later call."""
-        if self.draw == 0:
-            return
-        if self._nat is None:
-            self._seen = (float(self.stats[1]), float(self.stats[2]))
-        elif self._copied.query():
-            self._seen = (float(self._host[1]), float(self._host[2]))
+        """Pick up the last call's stats row if it has reached the host (a row still in flight: a later call does)."""
+        got = self._mirror.poll()
+        if got is not None:
+            self._seen = (float(got[1][1]), float(got[1][2]))
 
     def round_stats(self) -> dict:
         """``dp_norm`` / ``dp_scale`` of the newest call whose stats row has reached the host (on a GPU at worst the

@@ -30,13 +30,13 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import List, Tuple
+from typing import Tuple
 
 import torch
 
 from .. import native
-from .replicated import ReplicatedConfig, ReplicatedState
-from .robust import MAX_RANKS, RobustAgg
+from .replicated import ReplicatedConfig
+from .robust import MAX_RANKS, GatheredAgg
 
 KINDS = ("geomed",)
 MAX_ITERS = 64
@@ -91,91 +91,33 @@ def geomed_torch(rows: torch.Tensor, iters: int, nu: float) -> Tuple[torch.Tenso
     return z, hist
 
 
-class GeoMedAgg(ReplicatedState):
+class GeoMedAgg(GatheredAgg):
     """The geometric-median rule in the ``robust`` slot of a :class:`fedmi.parallel.fedavg.FedAvg`, with
-    :class:`fedmi.parallel.robust.RobustAgg`'s interface.  Stateless across rounds; holds the gather buffer, the
-    partials and the device history ``[T + 1][3][16]`` of the last call."""
+    :class:`fedmi.parallel.robust.RobustAgg`'s interface; ``history`` is ``[T + 1][3][16]`` of the last call."""
 
     def __init__(self, trainer, cfg: GeoMedConfig):
-        super().__init__(trainer.float_state(), cfg)
-        shape = (cfg.iters + 1, 3, MAX_RANKS)
-        self.history = torch.zeros(shape, dtype=torch.float64, device=self.dev)
-        self._rows = None                # [W, ld] gather buffer, ld = n rounded up to 4
-        self._partial = None             # fp64 [blocks, 16]
-        self._host = self._copied = None
+        self.history = torch.zeros((cfg.iters + 1, 3, MAX_RANKS), dtype=torch.float64,
+                                   device=trainer.float_state().device)
+        super().__init__(trainer, cfg, self.history)
+
+    def _reduce(self, rows, x, W, n):
+        T = self.cfg.iters
         if self._nat is not None:
-            self._host = torch.zeros(shape, dtype=torch.float64).pin_memory()
-            self._copied = torch.cuda.Event()
-        self._flying = None              # the world of the history on its way to the host
-        self._seen = None                # (weights, dists) of the newest history known on the host
-
-    def _rolled(self) -> List[torch.Tensor]:
-        return []
-
-    def state_tensors(self) -> List[torch.Tensor]:
-        return []
-
-    def reset(self, trainer) -> None:
-        pass
-
-    def _partials(self, rows: int) -> torch.Tensor:
-        if self._partial is None or self._partial.shape[0] < rows:
-            self._partial = torch.zeros((max(1, rows), MAX_RANKS), dtype=torch.float64, device=self.dev)
-        return self._partial
-
-    def aggregate(self, trainer, fedavg) -> None:
-        """``float_state()`` holds the client's model on entry and the geometric-median iterate of all clients' on
-        return (the same bits on every client)."""
-        W = fedavg.world()
-        if W < 2:
-            return
-        if W > MAX_RANKS:
-            raise ValueError(f"robust aggregation handles at most {MAX_RANKS} clients, the federation has {W}")
-        x = trainer.float_state()
-        n, T = x.numel(), self.cfg.iters
-        self._collect()                             # the previous call's history, before this one overwrites it
-        ld = (n + 3) & ~3                           # every row 16-byte aligned
-        if self._rows is None or tuple(self._rows.shape) != (W, ld):
-            self._rows = None                       # (the old one first)
-            self._rows = torch.zeros((W, ld), dtype=torch.float32, device=self.dev)
-        tp = fedavg.transport
-        if tp is not None:
-            self._rows[:, :n].copy_(tp.all_gather(x))
-        else:
-            RobustAgg._all_gather([self._rows[r, :n] for r in range(W)], x, fedavg.group, fedavg.abort)
-        if self._nat is not None:
-            self._nat.geomed(native.stream_handle(self.dev), self._rows.data_ptr(), ld, W, n, T, self.cfg.nu,
-                             x.data_ptr(), self._partials(self._nat.geomed_partials(n)).data_ptr(),
+            self._nat.geomed(native.stream_handle(self.dev), rows.data_ptr(), rows.shape[1], W, n, T, self.cfg.nu,
+                             x.data_ptr(), self._partials(self._nat.geomed_partials(n), torch.float64).data_ptr(),
                              self.history.data_ptr())
-            # the history reaches the host behind the launches; read at the next round's start (round_stats)
-            self._host.copy_(self.history, non_blocking=True)
-            self._copied.record(torch.cuda.current_stream(self.dev))
         else:
             with torch.no_grad():
-                z, hist = geomed_torch(self._rows[:, :n], T, self.cfg.nu)
+                z, hist = geomed_torch(rows[:, :n], T, self.cfg.nu)
                 x.copy_(z)
                 self.history[:, :, :W] = hist
-        self._flying = W
+        return W
 
-    def _collect(self) -> None:
-        """Pick up the last call's history if it has reached the host.  Never waits."""
-        if self._flying is None:
-            return
-        W, T = self._flying, self.cfg.iters
-        if self._nat is None:
-            h = self.history
-        elif self._copied.query():
-            h = self._host
-        else:
-            return
-        self._seen = (h[T - 1, 2, :W].tolist(), h[T, 1, :W].tolist())
+    def _decode(self, W, h) -> dict:
+        """``robust_weight`` (the weights that formed the aggregate) and ``robust_dist`` (every client's distance to it)."""
+        T = self.cfg.iters
+        return {"robust_weight": [float(v) for v in h[T - 1, 2, :W].tolist()],
+                "robust_dist": [float(v) for v in h[T, 1, :W].tolist()]}
 
     def round_stats(self) -> dict:
-        """``robust_kind``, ``robust_iters``, and ``robust_weight`` (the weights that formed the aggregate) /
-        ``robust_dist`` (every client's distance to it) of the newest call whose history has reached the host (on a
-        GPU at worst the previous round's: no sync is added)."""
-        self._collect()
-        rec = {"robust_kind": self.cfg.kind, "robust_iters": self.cfg.iters}
-        if self._seen is not None:
-            rec["robust_weight"], rec["robust_dist"] = [float(v) for v in self._seen[0]], [float(v) for v in self._seen[1]]
-        return rec
+        return {**super().round_stats(), "robust_iters": self.cfg.iters}

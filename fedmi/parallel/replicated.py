@@ -40,6 +40,34 @@ class ReplicatedConfig:
                                    f"the same {self.FLAG} settings{self.MISMATCH_TAIL}")
 
 
+class HostMirror:
+    """A small device tensor of per-round statistics and its pinned host twin.  :meth:`post` after the round's
+    launches sends the row to the host behind them; :meth:`poll` at the next round's start (or from ``round_stats``)
+    hands it over if it has arrived.  Nothing ever waits for it.  Off the GPU the tensor is its own twin."""
+
+    def __init__(self, stats: torch.Tensor):
+        self.stats = stats
+        self._host = self._copied = None
+        if stats.is_cuda:
+            self._host = torch.zeros(stats.shape, dtype=stats.dtype).pin_memory()
+            self._copied = torch.cuda.Event()
+        self._tag = None                 # of the row on its way to the host: what the owner needs to decode it
+
+    def post(self, tag=True) -> None:
+        self._tag = tag
+        if self._host is not None:
+            self._host.copy_(self.stats, non_blocking=True)
+            self._copied.record(torch.cuda.current_stream(self.stats.device))
+
+    def poll(self):
+        """``(tag, host tensor)`` of the last :meth:`post` if its row has reached the host, else None."""
+        if self._tag is None:
+            return None
+        if self._host is None:
+            return self._tag, self.stats
+        return (self._tag, self._host) if self._copied.query() else None
+
+
 class ReplicatedState:
     """Base of ``ServerOpt``, ``ClientOpt`` and ``DpGuard``, built from the trainer's flat float state ``x`` (it decides the
     device and whether the HIP kernels run).  A subclass says in ``_rolled()`` which tensors a void round must

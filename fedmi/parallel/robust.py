@@ -37,7 +37,7 @@ import torch
 import torch.distributed as dist
 
 from .. import native
-from .replicated import ReplicatedConfig, ReplicatedState
+from .replicated import HostMirror, ReplicatedConfig, ReplicatedState
 
 KINDS = ("median", "trimmed")
 MAX_RANKS = 16
@@ -91,23 +91,19 @@ def robust_reduce_torch(rows: torch.Tensor, b_eff: int) -> Tuple[torch.Tensor, t
     return out, torch.bincount(outside, minlength=W).to(torch.int64)
 
 
-class RobustAgg(ReplicatedState):
-    """The robust rule attached to a :class:`fedmi.parallel.fedavg.FedAvg`.  Stateless: nothing is rolled back or
+class GatheredAgg(ReplicatedState):
+    """Base of the rules that replace FedAvg's mean by a function of all clients' gathered float states
+    (:class:`RobustAgg`, :class:`fedmi.parallel.geomed.GeoMedAgg`).  Stateless across rounds: nothing is rolled back or
     handed over; the class exists so that ``resync`` compares the settings across clients and raises on the one that
-    differs.  Holds the gather buffer, the cut partials and the device stats row ``cut[0..16)`` of the last call."""
+    differs.  Holds the ``[W, ld]`` gather buffer, the kernels' partials and the host mirror of ``stats``, the device
+    statistics of the last call.  A subclass supplies :meth:`_reduce` and :meth:`_decode`."""
 
-    def __init__(self, trainer, cfg: RobustConfig):
+    def __init__(self, trainer, cfg: ReplicatedConfig, stats: torch.Tensor):
         super().__init__(trainer.float_state(), cfg)
-        self.stats = torch.zeros(MAX_RANKS, dtype=torch.int64, device=self.dev)
-        self._rows = None                # [W, ld] gather buffer (torch.distributed path), ld = n rounded up to 4
-        self._partial = None             # int64 [blocks, 16]
-        self._host = self._copied = None
-        if self._nat is not None:
-            self._host = torch.zeros(MAX_RANKS, dtype=torch.int64).pin_memory()
-            self._copied = torch.cuda.Event()
-        self._flying = None              # (b_eff, world) of the stats row on its way to the host
-        self._seen = None                # (b_eff, [cut]) of the newest row known on the host
-        self._warned = False
+        self._rows = None                # [W, ld] gather buffer, ld = n rounded up to 4
+        self._partial = None             # [blocks, 16], one row per workgroup of the sweep
+        self._mirror = HostMirror(stats)
+        self._seen = {}                  # the decoded statistics of the newest call known on the host
 
     def _rolled(self) -> List[torch.Tensor]:
         return []
@@ -118,13 +114,13 @@ class RobustAgg(ReplicatedState):
     def reset(self, trainer) -> None:
         pass
 
-    def _partials(self, rows: int) -> torch.Tensor:
+    def _partials(self, rows: int, dtype: torch.dtype) -> torch.Tensor:
         if self._partial is None or self._partial.shape[0] < rows:
-            self._partial = torch.zeros((max(1, rows), MAX_RANKS), dtype=torch.int64, device=self.dev)
+            self._partial = torch.zeros((max(1, rows), MAX_RANKS), dtype=dtype, device=self.dev)
         return self._partial
 
     def aggregate(self, trainer, fedavg) -> None:
-        """``float_state()`` holds the client's model on entry and the robust aggregate of all clients' on return
+        """``float_state()`` holds the client's model on entry and the rule's aggregate of all clients' on return
         (the same bits on every client).  ``fedavg`` supplies the world, the transport or group, and the abort flag."""
         W = fedavg.world()
         if W < 2:
@@ -132,37 +128,24 @@ class RobustAgg(ReplicatedState):
         if W > MAX_RANKS:
             raise ValueError(f"robust aggregation handles at most {MAX_RANKS} clients, the federation has {W}")
         x = trainer.float_state()
-        n, b = x.numel(), self.cfg.b_eff(W)
-        if b == 0 and not self._warned:
-            from ..utils.metrics import log
+        self._collect()                             # the previous call's statistics, before this one overwrites them
+        self._mirror.post(self._run(x, W, fedavg))
 
-            self._warned = True
-            log("robust", f"{W} clients: nothing can be trimmed (b_eff = 0), --robust {self.cfg.kind} is the plain "
-                          f"mean until the federation has 3 or more")
-        self._collect()                             # the previous call's row, before this one overwrites it
-        tp = fedavg.transport
-        if tp is not None:
-            tp.allreduce_robust_(x, b, self._partials(self._nat.PEER_MAX_BLOCKS), self.stats)
+    def _run(self, x: torch.Tensor, W: int, fedavg):
+        """Gather and reduce; returns what :meth:`_decode` needs besides the statistics."""
+        return self._reduce(self._gather(x, W, fedavg), x, W, x.numel())
+
+    def _gather(self, x: torch.Tensor, W: int, fedavg) -> torch.Tensor:
+        n = x.numel()
+        ld = (n + 3) & ~3                           # every row 16-byte aligned
+        if self._rows is None or tuple(self._rows.shape) != (W, ld):
+            self._rows = None                       # (the old one first: ResNet-18 at 8 clients is 358 MB)
+            self._rows = torch.zeros((W, ld), dtype=torch.float32, device=self.dev)
+        if fedavg.transport is not None:
+            self._rows[:, :n].copy_(fedavg.transport.all_gather(x))
         else:
-            ld = (n + 3) & ~3                       # every row 16-byte aligned
-            if self._rows is None or tuple(self._rows.shape) != (W, ld):
-                self._rows = None                   # (the old one first: ResNet-18 at 8 clients is 358 MB)
-                self._rows = torch.zeros((W, ld), dtype=torch.float32, device=self.dev)
             self._all_gather([self._rows[r, :n] for r in range(W)], x, fedavg.group, fedavg.abort)
-            if self._nat is not None:
-                self._nat.robust_reduce(native.stream_handle(self.dev), self._rows.data_ptr(), ld, W, n, b,
-                                        x.data_ptr(), self._partials(self._nat.robust_partials(n)).data_ptr(),
-                                        self.stats.data_ptr())
-            else:
-                with torch.no_grad():
-                    out, cut = robust_reduce_torch(self._rows[:, :n], b)
-                    x.copy_(out)
-                    self.stats[:W] = cut
-        self._flying = (b, W)
-        if self._nat is not None:
-            # the row reaches the host behind the launches; read at the next round's start (round_stats)
-            self._host.copy_(self.stats, non_blocking=True)
-            self._copied.record(torch.cuda.current_stream(self.dev))
+        return self._rows
 
     @staticmethod
     def _all_gather(rows, x, group, abort) -> None:
@@ -178,23 +161,56 @@ class RobustAgg(ReplicatedState):
         wait_work(dist.all_gather(rows, x, group=group, async_op=True), abort, "all_gather")
 
     def _collect(self) -> None:
-        """Pick up the last call's cut counts if they have reached the host.  Never waits."""
-        if self._flying is None:
-            return
-        b, W = self._flying
-        if self._nat is None:
-            self._seen = (b, self.stats[:W].tolist())
-        elif self._copied.query():
-            self._seen = (b, self._host[:W].tolist())
+        """Pick up the last call's statistics if they have reached the host.  Never waits."""
+        got = self._mirror.poll()
+        if got is not None:
+            self._seen = self._decode(*got)
 
     def round_stats(self) -> dict:
-        """``robust_kind``, and ``robust_trim`` (the effective one) / ``robust_cut`` (one count per client) of the
-        newest call whose stats row has reached the host (on a GPU at worst the previous round's: no sync is added)."""
+        """``robust_kind`` and :meth:`_decode`'s keys of the newest call whose statistics have reached the host (on a
+        GPU at worst the previous round's: no sync is added)."""
         self._collect()
-        rec = {"robust_kind": self.cfg.kind}
-        if self._seen is not None:
-            rec["robust_trim"], rec["robust_cut"] = self._seen[0], [int(c) for c in self._seen[1]]
-        return rec
+        return {"robust_kind": self.cfg.kind, **self._seen}
+
+
+class RobustAgg(GatheredAgg):
+    """The coordinate-wise rule attached to a :class:`fedmi.parallel.fedavg.FedAvg`; ``stats`` is ``cut[0..16)``."""
+
+    def __init__(self, trainer, cfg: RobustConfig):
+        self.stats = torch.zeros(MAX_RANKS, dtype=torch.int64, device=trainer.float_state().device)
+        super().__init__(trainer, cfg, self.stats)
+        self._warned = False
+
+    def _run(self, x, W, fedavg):
+        b = self.cfg.b_eff(W)
+        if b == 0 and not self._warned:
+            from ..utils.metrics import log
+
+            self._warned = True
+            log("robust", f"{W} clients: nothing can be trimmed (b_eff = 0), --robust {self.cfg.kind} is the plain "
+                          f"mean until the federation has 3 or more")
+        if fedavg.transport is None:
+            return super()._run(x, W, fedavg)
+        # the peer transport folds in its one-shot all-reduce: one kernel, no gather buffer
+        fedavg.transport.allreduce_robust_(x, b, self._partials(self._nat.PEER_MAX_BLOCKS, torch.int64), self.stats)
+        return b, W
+
+    def _reduce(self, rows, x, W, n):
+        b = self.cfg.b_eff(W)
+        if self._nat is not None:
+            self._nat.robust_reduce(native.stream_handle(self.dev), rows.data_ptr(), rows.shape[1], W, n, b,
+                                    x.data_ptr(), self._partials(self._nat.robust_partials(n), torch.int64).data_ptr(),
+                                    self.stats.data_ptr())
+        else:
+            with torch.no_grad():
+                out, cut = robust_reduce_torch(rows[:, :n], b)
+                x.copy_(out)
+                self.stats[:W] = cut
+        return b, W
+
+    def _decode(self, tag, stats) -> dict:
+        """``robust_trim`` (the effective one) and ``robust_cut`` (one count per client)."""
+        return {"robust_trim": tag[0], "robust_cut": [int(c) for c in stats[:tag[1]].tolist()]}
 
 
 def add_robust_flags(ap) -> None:

@@ -143,3 +143,28 @@ def test_drill_one_attacker_in_five():
     print(f"drill: reference {ref:.4f}, twin {got:.4f}, plain mean {plain:.4f}, weights {hist[5, 2].tolist()}")
     assert ref < 0.1 and got < 0.1 and plain > 1.0
     assert int(hist[5, 2].argmin()) == 4                 # the attacker is the client with the smallest weight
+
+
+@pytest.mark.parametrize("n,grid", [(5, 1), (1027, 1), (3077, 4), (3077, 2), (4103, 1)])
+def test_the_emulated_order_is_the_kernels_loops(n, grid):
+    """The vectorised emulation of the kernels' summation order equals the plain loops bit for bit, at the launcher's
+    grid and at smaller ones, where every lane strides two or five times."""
+    rows = gc.inputs_mixed(3, n)
+    z = gc.z_ref(rows)[0].astype(np.float32)
+    assert grid <= gc.flat_grid(n) == (4 if n == 3077 else 1 if n < 4103 else 5)
+    assert gc.sumsq_in_kernel_order(rows, z, grid).tobytes() == gc.sumsq_in_kernel_order_loops(rows, z, grid).tobytes()
+    assert gc.near(gc.sumsq_in_kernel_order(rows, z), gc.sumsq_ref(rows, z), (n + 256 + 2048) * gc.U64 * gc.sumsq_ref(rows, z))
+
+
+@pytest.mark.parametrize("W", [2, 5, 16])
+@pytest.mark.parametrize("n", [1027, 3077])
+def test_a_reordered_sum_is_caught(W, n):
+    """On the inputs of the GPU test of the order, a pairwise tree over the same exact terms (numpy's sum) and the
+    lanes' chains in rank-major blocks differ from the kernels' order in at least one bit: the bit-for-bit comparison
+    can tell a reordered sum from the original.  (At n = 5 one lane adds five terms in index order: nothing to reorder.)"""
+    rows = gc.inputs_mixed(W, n)
+    for w in (None, gc.weights(W)):
+        z = gc.z_ref(rows, w)[0].astype(np.float32)
+        right = gc.sumsq_in_kernel_order(rows, z)
+        assert gc.squares(rows, z).sum(1).tobytes() != right.tobytes()
+        assert np.cumsum(gc.squares(rows, z), axis=1)[:, -1].tobytes() != right.tobytes()     # one chain in index order

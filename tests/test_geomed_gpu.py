@@ -56,6 +56,22 @@ def test_one_pass_within_the_bounds(nat, gpu_device, W):
             gc.check_pass(rows, w, z, hist, NU, f"W={W} n={n} first={w is None}")
 
 
+@pytest.mark.parametrize("W", [2, 5, 16])
+def test_sumsq_is_added_in_the_documented_order(nat, gpu_device, W):
+    """The history's sumsq column equals, bit for bit, the kernel's own squared differences added in the order
+    geomed.hip documents (tests/geomed_check.py emulates it; tests/test_geomed.py shows that a reordered sum differs
+    on these inputs).  n = 5: one lane and a tail; 1027: one workgroup, a partly filled last wave, tail 3; 3077: four
+    workgroups, the last with a single vector, tail 1; BIG_N: every lane strides."""
+    for n in (5, 1027, 3077) + ((BIG_N,) if W in (2, 16) else ()):
+        rows = gc.inputs_mixed(W, n)
+        for w in (None, gc.weights(W)):
+            z, hist = _run(nat, gpu_device, rows, w, first=w is None)
+            want = gc.sumsq_in_kernel_order(rows, z)
+            print(f"W={W} n={n} first={w is None}: sumsq {hist[0][:W].tolist()} emulated {want.tolist()}")
+            assert hist[0][:W].tobytes() == want.tobytes(), f"W={W} n={n} first={w is None}"
+            gc.check_pass(rows, w, z, hist, NU, f"W={W} n={n} first={w is None} (mixed magnitudes)")
+
+
 @pytest.mark.parametrize("W,bad", [(3, 0), (5, 4), (16, 7)])
 @pytest.mark.parametrize("poison", ["nan-row", "one-inf"])
 def test_a_non_finite_row_gets_weight_zero_and_stays_out(nat, gpu_device, W, bad, poison):
@@ -104,7 +120,7 @@ def test_chain_link_by_link(nat, gpu_device, W, T):
 def test_aggregate_stats_and_drill(nat, gpu_device, monkeypatch):
     """GeoMedAgg.aggregate (the gather replaced by a copy of the clients' known states) equals the direct native call
     bit for bit, its lagged round_stats are the history's, and the drill's thresholds hold on the GPU."""
-    from fedmi.parallel.robust import RobustAgg
+    from fedmi.parallel.robust import GatheredAgg
 
     rows6 = drill_rows()
     rows = rows6[:5].copy()
@@ -113,7 +129,7 @@ def test_aggregate_stats_and_drill(nat, gpu_device, monkeypatch):
         for r, v in enumerate(views):
             v.copy_(torch.from_numpy(rows[r].copy()))
 
-    monkeypatch.setattr(RobustAgg, "_all_gather", staticmethod(fake_all_gather))
+    monkeypatch.setattr(GatheredAgg, "_all_gather", staticmethod(fake_all_gather))
     t = _GpuStub(torch.from_numpy(rows[1].copy()).to(gpu_device))
     agg = make_robust("geomed", t, iters=6)
     agg.aggregate(t, _FakeFedAvg(5))
