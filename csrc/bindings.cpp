@@ -43,6 +43,10 @@ int geomed_partials(long);
 void launch_geomed_pass(hipStream_t, const float*, long, int, long, bool, const float*, const double*, double, float*,
                         double*, double*, int);
 void launch_geomed(hipStream_t, const float*, long, int, long, int, double, float*, double*, double*);
+int secagg_partials(long);
+void launch_secagg_mask(hipStream_t, const float*, const float*, const uint32_t*, int, int, uint64_t, long, int,
+                        uint32_t*, long long*, long long*);
+void launch_secagg_unmask(hipStream_t, const float*, long, int, const float*, long, int, float*);
 void launch_ef_delta(hipStream_t, const float*, const float*, const float*, float*, long);
 size_t topk_state_bytes();
 size_t topk_overflow_offset();
@@ -298,6 +302,55 @@ static void fedmi_bind(py::module_& m) {
     check_last("geomed_pass");
   }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("first"),
      py::arg("weights"), py::arg("out"), py::arg("partial"), py::arg("history_row"), py::arg("nu") = 1e-6);
+
+  // secure aggregation by pairwise masking (csrc/kernels/secagg.hip).  secagg_mask: u[i] = the fixed-point word of
+  // x[i] - anchor[i] at frac_bits fraction bits plus the ChaCha20 masks of the W - 1 pairs of `rank` (keys: W x 8
+  // uint32, row `rank` unused; nonce = draw), stats[0] = the number of clamped or NaN entries.  partial:
+  // secagg_partials(n) x 16 int64.  secagg_unmask: out[i] = anchor[i] + (float)(sum_r rows[r][i] * 2^-frac_bits / W),
+  // the sum over the W gathered payload rows mod 2^32, read as int32.
+  m.def("secagg_partials", [](long n) {
+    if (n < 0) throw std::invalid_argument("secagg_partials: need n >= 0");
+    return secagg_partials(n);
+  });
+  auto secagg_check = [](const char* who, int W, long n, int frac_bits) {
+    const std::string p = std::string(who) + ": ";
+    if (W < 2 || W > 16) throw std::invalid_argument(p + "W must be in 2..16");
+    if (n < 0) throw std::invalid_argument(p + "need n >= 0");
+    if (frac_bits < 19 || frac_bits > 35) throw std::invalid_argument(p + "frac_bits must be in 19..35 (27 - log2 R)");
+  };
+  m.def("secagg_mask", [secagg_check](uintptr_t st, uintptr_t x, uintptr_t anchor, uintptr_t keys, int W, int rank,
+                                      uint64_t draw, long n, int frac_bits, uintptr_t u, uintptr_t partial,
+                                      uintptr_t stats) {
+    secagg_check("secagg_mask", W, n, frac_bits);
+    if (rank < 0 || rank >= W) throw std::invalid_argument("secagg_mask: need 0 <= rank < W");
+    if (n == 0) return;
+    if (!x || !anchor || !keys || !u || !partial || !stats) throw std::invalid_argument("secagg_mask: null buffer");
+    if ((x | anchor | u) % 16) throw std::invalid_argument("secagg_mask: x, anchor and u must be 16-byte aligned");
+    if (keys % 4 || (partial | stats) % 8)
+      throw std::invalid_argument("secagg_mask: keys must be 4-byte, partial and stats 8-byte aligned");
+    const uintptr_t bytes = (uintptr_t)n * 4;
+    if ((u < x + bytes && x < u + bytes) || (u < anchor + bytes && anchor < u + bytes))
+      throw std::invalid_argument("secagg_mask: u must not alias x or anchor");
+    launch_secagg_mask(S(st), P<const float>(x), P<const float>(anchor), P<const uint32_t>(keys), W, rank, draw, n,
+                       frac_bits, P<uint32_t>(u), P<long long>(partial), P<long long>(stats));
+    check_last("secagg_mask");
+  }, py::arg("stream"), py::arg("x"), py::arg("anchor"), py::arg("keys"), py::arg("W"), py::arg("rank"),
+     py::arg("draw"), py::arg("n"), py::arg("frac_bits"), py::arg("u"), py::arg("partial"), py::arg("stats"));
+  m.def("secagg_unmask", [secagg_check](uintptr_t st, uintptr_t rows, long ld, int W, uintptr_t anchor, long n,
+                                        int frac_bits, uintptr_t out) {
+    secagg_check("secagg_unmask", W, n, frac_bits);
+    if (ld < n || ld % 4) throw std::invalid_argument("secagg_unmask: the row stride ld must be >= n and a multiple of 4");
+    if (n == 0) return;
+    if (!rows || !anchor || !out) throw std::invalid_argument("secagg_unmask: null buffer");
+    if ((rows | anchor | out) % 16)
+      throw std::invalid_argument("secagg_unmask: rows, anchor and out must be 16-byte aligned");
+    const uintptr_t row_bytes = ((uintptr_t)(W - 1) * (uintptr_t)ld + (uintptr_t)n) * 4, bytes = (uintptr_t)n * 4;
+    if ((out < rows + row_bytes && rows < out + bytes) || (out < anchor + bytes && anchor < out + bytes))
+      throw std::invalid_argument("secagg_unmask: out must not alias rows or anchor");
+    launch_secagg_unmask(S(st), P<const float>(rows), ld, W, P<const float>(anchor), n, frac_bits, P<float>(out));
+    check_last("secagg_unmask");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("anchor"), py::arg("n"),
+     py::arg("frac_bits"), py::arg("out"));
 
   // client-side drift correction of the flat gradient, between the backward pass and the SGD tail (kind: 0
   // fedprox -- g, p, anchor, mu; 1 scaffold -- g, corr, acc); the other kind's buffers may be 0

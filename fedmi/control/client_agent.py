@@ -353,6 +353,9 @@ class ClientAgent(P.TrainerServicer):
             robust = getattr(self.fedavg, "robust", None)
             if robust is not None:
                 rec.update(robust.round_stats())    # who was cut, how often: no sync of its own either
+            secagg = getattr(self.fedavg, "secagg", None)
+            if secagg is not None:
+                rec.update(secagg.round_stats())    # the masks drawn so far, the entries clamped: no sync either
             self.round = rnd
             self._check_compressor(rnd)
             t4 = Timer()

@@ -102,11 +102,17 @@ class FedAvg:
     client_opt: Optional[object] = None      # fedmi.parallel.client_opt.ClientOpt (None: plain local SGD)
     dp: Optional[object] = None              # fedmi.parallel.dp.DpGuard (None: the raw update is aggregated)
     robust: Optional[object] = None          # fedmi.parallel.robust.RobustAgg (None: the plain mean)
+    secagg: Optional[object] = None          # fedmi.parallel.secagg.SecAgg (None: the update travels in the clear)
 
     def world(self) -> int:
         if self.transport is not None:
             return self.transport.world
         return _world(self.group)
+
+    def rank(self) -> int:
+        if self.transport is not None:
+            return self.transport.rank
+        return dist.get_rank(self.group) if dist.is_available() and dist.is_initialized() else 0
 
     def label(self) -> str:
         """What actually carries the aggregation (reported by the benches)."""
@@ -125,8 +131,8 @@ class FedAvg:
 
     def opts(self) -> list:
         """The attached :class:`fedmi.parallel.replicated.ReplicatedState`: server and client optimizer, DP guard,
-        robust rule."""
-        return [o for o in (self.server_opt, self.client_opt, self.dp, self.robust) if o is not None]
+        robust rule, secure-aggregation guard."""
+        return [o for o in (self.server_opt, self.client_opt, self.dp, self.robust, self.secagg) if o is not None]
 
     def snapshot_opts(self) -> None:
         for o in self.opts():
@@ -163,6 +169,9 @@ class FedAvg:
                 # the coordinate-wise median / trimmed mean of the clients' (clipped) models instead of their mean;
                 # the server step below takes it as its end point
                 self.robust.aggregate(trainer, self)
+            elif self.secagg is not None:
+                # the same mean, of fixed-point updates under pairwise masks: no peer sees this client's model
+                self.secagg.aggregate(trainer, self)
             else:
                 self._mean(trainer.float_state())
             for b in trainer.int_state():
@@ -188,6 +197,8 @@ class FedAvg:
             co.begin_round(trainer, co.delta)
         if self.dp is not None:
             self.dp.begin_round(trainer)      # the next round's update is measured from this model
+        if self.secagg is not None:
+            self.secagg.begin_round(trainer)
         trainer.after_aggregate()
         dt = (time.perf_counter() - t0) * 1e3
         self.timer.last_ms = dt

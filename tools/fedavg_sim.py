@@ -151,6 +151,10 @@ def _run_seed(a, seed, data, dev, out) -> None:
     dps = [make_dp(a.dp_clip, tr, a.dp_noise, a.dp_delta, a.dp_seed, who=f"seed{seed}/client{r}")
            for r, tr in enumerate(clients)]
     robust = make_robust(a.robust, clients[0], a.robust_trim, a.robust_iters, a.robust_nu)
+    # one secure-aggregation guard per simulated client: its own secret, anchor and pair keys, one shared draw count
+    from fedmi.parallel.secagg import make_secagg, secagg_stack
+
+    sas = [make_secagg(a.secagg, tr, a.secagg_range, a.secagg_seed) for tr in clients]
     for rnd in range(1, a.rounds + 1):
         t0 = time.perf_counter()
         tstats = []
@@ -173,6 +177,8 @@ def _run_seed(a, seed, data, dev, out) -> None:
             cut = None
             if robust is not None and W > 1:
                 mean, cut = robust_stack(robust, [tr.float_state() for tr in clients])
+            elif sas[0] is not None and W > 1:
+                mean = secagg_stack(sas, [tr.float_state() for tr in clients])
             else:
                 mean = torch.stack([tr.float_state() for tr in clients]).mean(0)
             ints = [torch.div(sum(bs), W, rounding_mode="floor")
@@ -192,6 +198,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
             for tr, dp in zip(clients, dps):
                 if dp is not None:
                     dp.begin_round(tr)
+            for tr, sa in zip(clients, sas):
+                if sa is not None:
+                    sa.begin_round(tr)
         if a.bn_eval == "batch":
             _eval_batch_bn(clients[0])
         else:
@@ -223,6 +232,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
         elif robust is not None:
             rec.update(robust_kind=a.robust, robust_trim=robust.cfg.b_eff(W),
                        robust_cut=cut.tolist() if cut is not None else None)
+        if sas[0] is not None:
+            sas[0]._mirror.post()                       # the eval above synchronised: this round's count is there
+            rec.update(secagg_range=a.secagg_range, **sas[0].round_stats())
         if a.attack != "none":
             rec.update(attack=a.attack, attackers=a.attackers, attack_scale=a.attack_scale)
         line = json.dumps(rec)
@@ -267,6 +279,9 @@ def main(argv=None) -> int:
     from fedmi.parallel.robust import add_robust_flags, check_robust_flags
 
     add_robust_flags(ap)
+    from fedmi.parallel.secagg import add_secagg_flags, check_secagg_flags
+
+    add_secagg_flags(ap)
     ap.add_argument("--attack", default="none", choices=list(ATTACKS),
                     help="simulated Byzantine clients (the simulator only): the last --attackers clients send "
                          "start - A (x - start) (signflip), start + A (x - start) (scale) or all NaN (nan) instead of "
@@ -278,6 +293,9 @@ def main(argv=None) -> int:
         ap.error("--client-mu must be >= 0")
     check_dp_flags(a, ap.error)
     check_robust_flags(a, ap.error)
+    check_secagg_flags(a, ap.error)
+    if a.secagg and a.clients > 16:
+        ap.error("--secagg handles at most 16 clients")
     if a.attack != "none" and not 1 <= a.attackers <= a.clients:
         ap.error("--attackers must lie in 1..--clients")
     if a.bn_eval == "batch" and a.engine == "native":
