@@ -43,6 +43,9 @@ int geomed_partials(long);
 void launch_geomed_pass(hipStream_t, const float*, long, int, long, bool, const float*, const double*, double, float*,
                         double*, double*, int);
 void launch_geomed(hipStream_t, const float*, long, int, long, int, double, float*, double*, double*);
+int krum_partials(long);
+void launch_krum_gram(hipStream_t, const float*, long, int, long, double*, double*);
+void launch_krum(hipStream_t, const float*, long, int, long, int, bool, float*, double*, double*);
 int secagg_partials(long);
 void launch_secagg_mask(hipStream_t, const float*, const float*, const uint32_t*, int, int, uint64_t, long, int,
                         uint32_t*, long long*, long long*);
@@ -302,6 +305,33 @@ static void fedmi_bind(py::module_& m) {
     check_last("geomed_pass");
   }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("first"),
      py::arg("weights"), py::arg("out"), py::arg("partial"), py::arg("history_row"), py::arg("nu") = 1e-6);
+
+  // Krum / multi-Krum aggregation (csrc/kernels/krum.hip): out = the client of lowest score (multi: the mean of the
+  // W - F_eff lowest), a client's score being the sum of its k smallest squared distances to the others, F_eff =
+  // max(0, min(byz, (W - 3) / 2)), k = max(1, W - F_eff - 2).  partial: krum_partials(n) x 256 doubles of scratch;
+  // stats: 18 x 16 doubles = score, selected (1.0 / 0.0) and the 16 x 16 squared distances.
+  m.def("krum_partials", [](long n) {
+    if (n < 0) throw std::invalid_argument("krum_partials: need n >= 0");
+    return krum_partials(n);
+  });
+  m.def("krum", [rows_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, int byz, bool multi, uintptr_t out,
+                             uintptr_t partial, uintptr_t stats) {
+    rows_check("krum", rows, ld, W, n, out, partial, stats);
+    if (byz < 0) throw std::invalid_argument("krum: need byz >= 0");
+    if (n == 0) return;
+    launch_krum(S(st), P<const float>(rows), ld, W, n, byz, multi, P<float>(out), P<double>(partial), P<double>(stats));
+    check_last("krum");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("byz"), py::arg("multi"),
+     py::arg("out"), py::arg("partial"), py::arg("stats"));
+  // the Gram pass and its fold alone: gram = G = X X^T as 16 x 16 doubles, 0 outside W x W (nothing else is written)
+  m.def("krum_gram", [rows_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, uintptr_t partial,
+                                  uintptr_t gram) {
+    rows_check("krum_gram", rows, ld, W, n, gram, partial, gram);
+    if (n == 0) return;
+    launch_krum_gram(S(st), P<const float>(rows), ld, W, n, P<double>(partial), P<double>(gram));
+    check_last("krum_gram");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("partial"),
+     py::arg("gram"));
 
   // secure aggregation by pairwise masking (csrc/kernels/secagg.hip).  secagg_mask: u[i] = the fixed-point word of
   // x[i] - anchor[i] at frac_bits fraction bits plus the ChaCha20 masks of the W - 1 pairs of `rank` (keys: W x 8

@@ -123,7 +123,7 @@ def main(argv=None) -> int:
     fedavg = FedAvg(compressor=make_compressor(comp_kind, a.topk_ratio, trainer, a.compress_warmup),
                     client_opt=client_opt,
                     dp=make_dp(a.dp_clip, trainer, a.dp_noise, a.dp_delta, a.dp_seed, who=a.address),
-                    robust=make_robust(a.robust, trainer, a.robust_trim, a.robust_iters, a.robust_nu),
+                    robust=make_robust(a.robust, trainer, a.robust_trim, a.robust_iters, a.robust_nu, a.robust_byz),
                     secagg=make_secagg(a.secagg, trainer, a.secagg_range, a.secagg_seed),
                     server_opt=make_server_opt(a.server_opt, trainer, a.server_lr, a.server_beta1, a.server_beta2,
                                                a.server_tau))

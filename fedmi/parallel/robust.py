@@ -93,7 +93,8 @@ def robust_reduce_torch(rows: torch.Tensor, b_eff: int) -> Tuple[torch.Tensor, t
 
 class GatheredAgg(ReplicatedState):
     """Base of the rules that replace FedAvg's mean by a function of all clients' gathered float states
-    (:class:`RobustAgg`, :class:`fedmi.parallel.geomed.GeoMedAgg`).  Stateless across rounds: nothing is rolled back or
+    (:class:`RobustAgg`, :class:`fedmi.parallel.geomed.GeoMedAgg`,
+    :class:`fedmi.parallel.krum.KrumAgg`).  Stateless across rounds: nothing is rolled back or
     handed over; the class exists so that ``resync`` compares the settings across clients and raises on the one that
     differs.  Holds the ``[W, ld]`` gather buffer, the kernels' partials and the host mirror of ``stats``, the device
     statistics of the last call.  A subclass supplies :meth:`_reduce` and :meth:`_decode`."""
@@ -214,12 +215,13 @@ class RobustAgg(GatheredAgg):
 
 
 def add_robust_flags(ap) -> None:
-    """``--robust``, ``--robust-trim``, ``--robust-iters`` and ``--robust-nu`` (fedmi.cli.client,
+    """``--robust``, ``--robust-trim``, ``--robust-iters``, ``--robust-nu`` and ``--robust-byz`` (fedmi.cli.client,
     tools/fedavg_sim.py)."""
-    ap.add_argument("--robust", default="none", choices=["none", *KINDS, "geomed"],
+    ap.add_argument("--robust", default="none", choices=["none", *KINDS, "geomed", "krum", "multikrum"],
                     help="Byzantine-robust aggregation (fedmi.parallel.robust): the coordinate-wise median or trimmed "
                          "mean of the clients' models replaces the plain mean; every client must pass the same settings."
-                         "  geomed (fedmi.parallel.geomed): the geometric median of the clients' whole models")
+                         "  geomed (fedmi.parallel.geomed): the geometric median of the clients' whole models.  krum / "
+                         "multikrum (fedmi.parallel.krum): the client nearest to its peers, or the mean of the nearest")
     ap.add_argument("--robust-trim", type=int, default=1, metavar="B",
                     help="trimmed: cut the B smallest and the B largest values of every coordinate (at most "
                          "(clients - 1) // 2 are cut: a shrinking federation degrades towards the median)")
@@ -227,6 +229,9 @@ def add_robust_flags(ap) -> None:
                     help="geomed: weighted Weiszfeld passes after the starting mean (1..64)")
     ap.add_argument("--robust-nu", type=float, default=1e-6, metavar="NU",
                     help="geomed: the floor of a client's distance in its weight 1 / max(NU, distance)")
+    ap.add_argument("--robust-byz", type=int, default=1, metavar="F",
+                    help="krum / multikrum: the number of arbitrary clients to withstand (at most (clients - 3) // 2 "
+                         "count: a shrinking federation degrades and does not fail)")
 
 
 def check_robust_flags(a, error) -> None:
@@ -239,6 +244,8 @@ def check_robust_flags(a, error) -> None:
         error("--robust-iters must lie in 1..64 (the weighted passes of the geometric median)")
     if not getattr(a, "robust_nu", 1e-6) > 0:
         error("--robust-nu must be > 0 (the smoothing floor of a client's distance)")
+    if getattr(a, "robust_byz", 1) < 1:
+        error("--robust-byz must be >= 1 (the number of arbitrary clients Krum withstands)")
     if getattr(a, "agg", "collective") == "grpc":
         error("--robust needs --agg collective: with --agg grpc the coordinator averages the clients' models "
               "(reference peers), nothing folds them robustly")
@@ -254,10 +261,15 @@ def check_robust_flags(a, error) -> None:
               "statistic of individually noised updates is not a post-processing of the sum (--dp-clip alone is fine)")
 
 
-def make_robust(kind: Optional[str], trainer=None, trim: int = 1, iters: int = 8, nu: float = 1e-6):
-    """None for ``none`` (nothing new is launched); a :class:`fedmi.parallel.geomed.GeoMedAgg` for ``geomed``."""
+def make_robust(kind: Optional[str], trainer=None, trim: int = 1, iters: int = 8, nu: float = 1e-6, byz: int = 1):
+    """None for ``none`` (nothing new is launched); a :class:`fedmi.parallel.geomed.GeoMedAgg` for ``geomed``, a
+    :class:`fedmi.parallel.krum.KrumAgg` for ``krum`` and ``multikrum``."""
     if kind in (None, "", "none"):
         return None
+    if kind in ("krum", "multikrum"):
+        from .krum import KrumAgg, KrumConfig
+
+        return KrumAgg(trainer, KrumConfig(kind, byz))
     if kind == "geomed":
         from .geomed import GeoMedAgg, GeoMedConfig
 

@@ -50,6 +50,8 @@ def robust_stack(robust, states, nat=None):
     W, n = len(states), states[0].numel()
     if robust.cfg.kind == "geomed":
         return geomed_stack(robust, states, nat)
+    if robust.cfg.kind in ("krum", "multikrum"):
+        return krum_stack(robust, states, nat)
     b = robust.cfg.b_eff(W)
     if not states[0].is_cuda:
         return robust_reduce_torch(torch.stack(states), b)
@@ -88,6 +90,29 @@ def geomed_stack(robust, states, nat=None):
     nat.geomed(native.stream_handle(dev), rows.data_ptr(), ld, W, n, T, robust.cfg.nu, out.data_ptr(),
                partial.data_ptr(), history.data_ptr())
     return out, history[:, :, :W]
+
+
+def krum_stack(robust, states, nat=None):
+    """The Krum / multi-Krum aggregate of the simulated clients' float states and its stats ``[18, 16]`` (score,
+    selected, the squared distances): ``krum`` (csrc/kernels/krum.hip) on a GPU, its torch twin elsewhere."""
+    from fedmi import native
+    from fedmi.parallel.krum import STATS_ROWS, krum_torch
+
+    W, n, cfg = len(states), states[0].numel(), robust.cfg
+    if not states[0].is_cuda:
+        return krum_torch(torch.stack(states), cfg.byz, cfg.multi)
+    nat = nat or native.require()
+    dev = states[0].device
+    ld = (n + 3) & ~3
+    rows = torch.zeros((W, ld), dtype=torch.float32, device=dev)
+    for r, x in enumerate(states):
+        rows[r, :n].copy_(x)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    partial = torch.zeros((max(1, nat.krum_partials(n)), 256), dtype=torch.float64, device=dev)
+    stats = torch.zeros((STATS_ROWS, 16), dtype=torch.float64, device=dev)
+    nat.krum(native.stream_handle(dev), rows.data_ptr(), ld, W, n, cfg.byz, cfg.multi, out.data_ptr(),
+             partial.data_ptr(), stats.data_ptr())
+    return out, stats
 
 
 def _eval_batch_bn(tr) -> None:
@@ -150,7 +175,7 @@ def _run_seed(a, seed, data, dev, out) -> None:
     # one DP guard per simulated client: its own key, anchor and draw counter; each adds its 1/sqrt(W) noise share
     dps = [make_dp(a.dp_clip, tr, a.dp_noise, a.dp_delta, a.dp_seed, who=f"seed{seed}/client{r}")
            for r, tr in enumerate(clients)]
-    robust = make_robust(a.robust, clients[0], a.robust_trim, a.robust_iters, a.robust_nu)
+    robust = make_robust(a.robust, clients[0], a.robust_trim, a.robust_iters, a.robust_nu, a.robust_byz)
     # one secure-aggregation guard per simulated client: its own secret, anchor and pair keys, one shared draw count
     from fedmi.parallel.secagg import make_secagg, secagg_stack
 
@@ -229,6 +254,11 @@ def _run_seed(a, seed, data, dev, out) -> None:
             rec.update(robust_kind=a.robust, robust_iters=T,
                        robust_weight=cut[T - 1, 2].tolist() if cut is not None else None,
                        robust_dist=cut[T, 1].tolist() if cut is not None else None)
+        elif robust is not None and a.robust in ("krum", "multikrum"):
+            # cut is the stats here: the scores and the selection
+            rec.update(robust_kind=a.robust, robust_byz=robust.cfg.counts(W)[0],
+                       robust_selected=[r for r in range(W) if float(cut[1, r]) == 1.0] if cut is not None else None,
+                       robust_score=cut[0, :W].tolist() if cut is not None else None)
         elif robust is not None:
             rec.update(robust_kind=a.robust, robust_trim=robust.cfg.b_eff(W),
                        robust_cut=cut.tolist() if cut is not None else None)
