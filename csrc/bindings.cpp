@@ -46,6 +46,9 @@ void launch_geomed(hipStream_t, const float*, long, int, long, int, double, floa
 int krum_partials(long);
 void launch_krum_gram(hipStream_t, const float*, long, int, long, double*, double*);
 void launch_krum(hipStream_t, const float*, long, int, long, int, bool, float*, double*, double*);
+int bulyan_partials(long);
+void launch_bulyan(hipStream_t, const float*, long, int, long, int, float*, double*, double*);
+void launch_bulyan_fold(hipStream_t, const float*, long, int, long, const int*, int, int, float*, double*, double*);
 int secagg_partials(long);
 void launch_secagg_mask(hipStream_t, const float*, const float*, const uint32_t*, int, int, uint64_t, long, int,
                         uint32_t*, long long*, long long*);
@@ -332,6 +335,42 @@ static void fedmi_bind(py::module_& m) {
     check_last("krum_gram");
   }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("partial"),
      py::arg("gram"));
+
+  // Bulyan aggregation (csrc/kernels/bulyan.hip): Krum, iterated over the one Gram matrix, selects theta = W - 2 F_eff
+  // clients, F_eff = max(0, min(byz, (W - 3) / 4)); out = per coordinate the mean of the theta - 2 F_eff of their values
+  // closest to the median.  partial: bulyan_partials(n) x 256 doubles of scratch; stats: 19 x 16 doubles = the score
+  // when picked, the round picked (0: never), the 16 x 16 squared distances and the per-client cut counts.
+  m.def("bulyan_partials", [](long n) {
+    if (n < 0) throw std::invalid_argument("bulyan_partials: need n >= 0");
+    return bulyan_partials(n);
+  });
+  m.def("bulyan", [rows_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, int byz, uintptr_t out,
+                               uintptr_t partial, uintptr_t stats) {
+    rows_check("bulyan", rows, ld, W, n, out, partial, stats);
+    if (byz < 0) throw std::invalid_argument("bulyan: need byz >= 0");
+    if (n == 0) return;
+    launch_bulyan(S(st), P<const float>(rows), ld, W, n, byz, P<float>(out), P<double>(partial), P<double>(stats));
+    check_last("bulyan");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("byz"), py::arg("out"),
+     py::arg("partial"), py::arg("stats"));
+  // the fold and its cut counts alone over the rows named by `record` (the selected ranks, ascending), dropping c values
+  // per coordinate: out and stats row 18 (nothing else of stats is written)
+  m.def("bulyan_fold", [rows_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, const std::vector<int>& record,
+                                    int c, uintptr_t out, uintptr_t partial, uintptr_t stats) {
+    rows_check("bulyan_fold", rows, ld, W, n, out, partial, stats);
+    const int theta = (int)record.size();
+    if (theta < 2 || theta > W) throw std::invalid_argument("bulyan_fold: the record must name 2..W clients");
+    for (int s = 0; s < theta; ++s)
+      if (record[s] < 0 || record[s] >= W || (s > 0 && record[s] <= record[s - 1]))
+        throw std::invalid_argument("bulyan_fold: the record must hold ascending ranks below W");
+    if (c < 0 || c > 6 || c % 2 || c >= theta)
+      throw std::invalid_argument("bulyan_fold: c must be 0, 2, 4 or 6 and leave one value");
+    if (n == 0) return;
+    launch_bulyan_fold(S(st), P<const float>(rows), ld, W, n, record.data(), theta, c, P<float>(out),
+                       P<double>(partial), P<double>(stats));
+    check_last("bulyan_fold");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("record"), py::arg("c"),
+     py::arg("out"), py::arg("partial"), py::arg("stats"));
 
   // secure aggregation by pairwise masking (csrc/kernels/secagg.hip).  secagg_mask: u[i] = the fixed-point word of
   // x[i] - anchor[i] at frac_bits fraction bits plus the ChaCha20 masks of the W - 1 pairs of `rank` (keys: W x 8

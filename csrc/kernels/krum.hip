@@ -28,6 +28,7 @@
 #include <math.h>
 
 #include "flat_map.h"
+#include "krum_gram.h"
 #include "robust_fold.h"
 
 namespace {
@@ -39,9 +40,6 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 constexpr int KR_THREADS = 256;
 constexpr int KR_WAVES = KR_THREADS / 64;
 constexpr int KR_STEPS = 4;                         // steps per chunk: four 16-B loads in flight per lane
-constexpr int KR_TILE = kRobustMaxRanks * kRobustMaxRanks;
-constexpr int KR_MAX_GRID = 1024;                   // 256 CUs x 4 workgroups: the whole grid is resident
-constexpr int KR_COLS_PER_WG = 1024;                // below the cap a workgroup takes this many columns
 constexpr int KR_STATS_ROWS = 2 + kRobustMaxRanks;
 
 template <int P>
@@ -93,24 +91,6 @@ __global__ __launch_bounds__(KR_THREADS) void krum_gram_kernel(const float* rows
     }
     partial[(long)blockIdx.x * (P * P) + threadIdx.x] = s;
   }
-}
-
-// fold_partial_rows' sibling for tiles: n_partial rows of E = P * P doubles (E = 16, 64 or 256); returns in lane t the
-// sum of entry t % E.  Lane (g, e), g = t / E, adds rows g, g + 1024 / E, .. in that order from 0, then a binary LDS
-// tree folds the 1024 / E groups (slot += slot + s for s = 512 .. E).
-FEDMI_DEV double fold_partial_tiles(const double* partial, int n_partial, int E) {
-  __shared__ double sh[kFoldThreads];
-  const int e = threadIdx.x % E, g = threadIdx.x / E;
-  double acc = 0.0;
-#pragma unroll 4
-  for (int i = g; i < n_partial; i += kFoldThreads / E) acc += partial[(long)i * E + e];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kFoldThreads / 2; s >= E; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[e];
 }
 
 // One workgroup.  gram != null: only G is written ([16][16], 0 outside W x W) -- the test's entry.  Otherwise stats and
@@ -197,12 +177,9 @@ struct KrumSelect {
   }
 };
 
-int krum_grid(long n) {
-  long blocks = (n + KR_COLS_PER_WG - 1) / KR_COLS_PER_WG;
-  return (int)(blocks < 1 ? 1 : blocks > KR_MAX_GRID ? KR_MAX_GRID : blocks);
-}
+}  // namespace
 
-int krum_tile(int W) { return W <= 4 ? 4 : W <= 8 ? 8 : 16; }
+namespace fedmi {
 
 void launch_gram_pass(hipStream_t st, const float* rows, long ld, int W, long n, double* partial) {
   const int grid = krum_grid(n);
@@ -212,10 +189,6 @@ void launch_gram_pass(hipStream_t st, const float* rows, long ld, int W, long n,
     default: hipLaunchKernelGGL(krum_gram_kernel<16>, dim3(grid), dim3(KR_THREADS), 0, st, rows, ld, W, n, partial);
   }
 }
-
-}  // namespace
-
-namespace fedmi {
 
 // rows of 256 doubles in `partial`: one per workgroup of the Gram pass (a function of n only, at most 1024) and one
 // for the record

@@ -1,0 +1,40 @@
+// fedmi — what the rules built on the fp64 Gram pass share (krum.hip, bulyan.hip): the grid and tile rules, the fold of
+// the pass's partial tiles, and the launcher of the pass itself (the kernel lives in krum.hip).
+#pragma once
+#include "robust_fold.h"
+
+namespace fedmi {
+
+constexpr int KR_TILE = kRobustMaxRanks * kRobustMaxRanks;
+constexpr int KR_MAX_GRID = 1024;                   // 256 CUs x 4 workgroups: the whole grid is resident
+constexpr int KR_COLS_PER_WG = 1024;                // below the cap a workgroup takes this many columns
+
+inline int krum_grid(long n) {
+  long blocks = (n + KR_COLS_PER_WG - 1) / KR_COLS_PER_WG;
+  return (int)(blocks < 1 ? 1 : blocks > KR_MAX_GRID ? KR_MAX_GRID : blocks);
+}
+
+inline int krum_tile(int W) { return W <= 4 ? 4 : W <= 8 ? 8 : 16; }
+
+// partial[wg] = the workgroup's share of G = X X^T as krum_tile(W)^2 doubles, wg < krum_grid(n)  (krum.hip)
+void launch_gram_pass(hipStream_t st, const float* rows, long ld, int W, long n, double* partial);
+
+// fold_partial_rows' sibling for tiles: n_partial rows of E = P * P doubles (E = 16, 64 or 256); returns in lane t the
+// sum of entry t % E.  Lane (g, e), g = t / E, adds rows g, g + 1024 / E, .. in that order from 0, then a binary LDS
+// tree folds the 1024 / E groups (slot += slot + s for s = 512 .. E).
+FEDMI_DEV double fold_partial_tiles(const double* partial, int n_partial, int E) {
+  __shared__ double sh[kFoldThreads];
+  const int e = threadIdx.x % E, g = threadIdx.x / E;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int i = g; i < n_partial; i += kFoldThreads / E) acc += partial[(long)i * E + e];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = kFoldThreads / 2; s >= E; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[e];
+}
+
+}  // namespace fedmi

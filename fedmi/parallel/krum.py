@@ -29,8 +29,8 @@ client still computes the same bits from the same rows.
 
 The float state is gathered as for the other rules (:class:`fedmi.parallel.robust.GatheredAgg`) and reduced by ``krum``
 (csrc/kernels/krum.hip: the Gram as fp64 MFMA tiles, a one-workgroup finish, a copy of the selected rows; three
-launches, no host sync) on a GPU or by :func:`krum_torch` on the CPU.  Not built: a fused peer kernel, Bulyan, client
-subsampling, a centred Gram.
+launches, no host sync) on a GPU or by :func:`krum_torch` on the CPU.  Bulyan builds on the same Gram pass
+(:mod:`fedmi.parallel.bulyan`).  Not built: a fused peer kernel, client subsampling, a centred Gram.
 """
 from __future__ import annotations
 

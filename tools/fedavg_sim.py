@@ -52,6 +52,8 @@ def robust_stack(robust, states, nat=None):
         return geomed_stack(robust, states, nat)
     if robust.cfg.kind in ("krum", "multikrum"):
         return krum_stack(robust, states, nat)
+    if robust.cfg.kind == "bulyan":
+        return bulyan_stack(robust, states, nat)
     b = robust.cfg.b_eff(W)
     if not states[0].is_cuda:
         return robust_reduce_torch(torch.stack(states), b)
@@ -112,6 +114,29 @@ def krum_stack(robust, states, nat=None):
     stats = torch.zeros((STATS_ROWS, 16), dtype=torch.float64, device=dev)
     nat.krum(native.stream_handle(dev), rows.data_ptr(), ld, W, n, cfg.byz, cfg.multi, out.data_ptr(),
              partial.data_ptr(), stats.data_ptr())
+    return out, stats
+
+
+def bulyan_stack(robust, states, nat=None):
+    """The Bulyan aggregate of the simulated clients' float states and its stats ``[19, 16]`` (score, round picked,
+    the squared distances, the cut counts): ``bulyan`` (csrc/kernels/bulyan.hip) on a GPU, its torch twin elsewhere."""
+    from fedmi import native
+    from fedmi.parallel.bulyan import STATS_ROWS, bulyan_torch
+
+    W, n, cfg = len(states), states[0].numel(), robust.cfg
+    if not states[0].is_cuda:
+        return bulyan_torch(torch.stack(states), cfg.byz)
+    nat = nat or native.require()
+    dev = states[0].device
+    ld = (n + 3) & ~3
+    rows = torch.zeros((W, ld), dtype=torch.float32, device=dev)
+    for r, x in enumerate(states):
+        rows[r, :n].copy_(x)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    partial = torch.zeros((max(1, nat.bulyan_partials(n)), 256), dtype=torch.float64, device=dev)
+    stats = torch.zeros((STATS_ROWS, 16), dtype=torch.float64, device=dev)
+    nat.bulyan(native.stream_handle(dev), rows.data_ptr(), ld, W, n, cfg.byz, out.data_ptr(), partial.data_ptr(),
+               stats.data_ptr())
     return out, stats
 
 
@@ -259,6 +284,12 @@ def _run_seed(a, seed, data, dev, out) -> None:
             rec.update(robust_kind=a.robust, robust_byz=robust.cfg.counts(W)[0],
                        robust_selected=[r for r in range(W) if float(cut[1, r]) == 1.0] if cut is not None else None,
                        robust_score=cut[0, :W].tolist() if cut is not None else None)
+        elif robust is not None and a.robust == "bulyan":
+            # cut is the stats here: the scores, the rounds of the selection and the cut counts
+            rec.update(robust_kind=a.robust, robust_byz=robust.cfg.counts(W)[0],
+                       robust_selected=[r for r in range(W) if float(cut[1, r]) > 0.0] if cut is not None else None,
+                       robust_score=cut[0, :W].tolist() if cut is not None else None,
+                       robust_cut=[int(v) for v in cut[18, :W].tolist()] if cut is not None else None)
         elif robust is not None:
             rec.update(robust_kind=a.robust, robust_trim=robust.cfg.b_eff(W),
                        robust_cut=cut.tolist() if cut is not None else None)
