@@ -60,6 +60,15 @@ void launch_topk_ef(hipStream_t, const float*, const float*, float*, long, int, 
 void launch_scatter_add_ranked(hipStream_t, float*, const int*, const float*, int, long, float, long);
 void launch_quant_int8(hipStream_t, const float*, long, signed char*, float*, float*);
 void launch_dequant_accum(hipStream_t, const signed char*, const float*, int, long, float*, float);
+void psgd_geometry(int (&)[11]);
+void launch_psgd_qinit(hipStream_t, float*, long, uint64_t);
+void launch_psgd_project(hipStream_t, const float*, const float*, float*, const void*, const void*, int, const float*, int,
+                         float*, float*, const void*, int);
+void launch_psgd_orth(hipStream_t, const void*, int, float*, int);
+void launch_psgd_backproject(hipStream_t, const float*, const void*, const void*, int, const float*, int, float*, float*,
+                             const void*, int);
+void launch_psgd_apply(hipStream_t, float*, float*, float*, const void*, const void*, int, const float*, const float*,
+                       const float*, int);
 }  // namespace fedmi
 
 using namespace fedmi;
@@ -500,6 +509,73 @@ static void fedmi_bind(py::module_& m) {
     launch_dequant_accum(S(st), P<const signed char>(q), P<const float>(scales), R, n, P<float>(out), scale);
     check_last("dequant_accum");
   });
+
+  // PowerSGD (csrc/kernels/powersgd.hip).  segs / tiles / folds are the device tables fedmi.parallel.compress.psgd_tables
+  // builds and checks against the buffers' sizes (the kernels trust them); a launch covers every segment.  part: the
+  // pass's partial buffer (may be 0 when nfolds == 0: no matrix was split).
+  m.def("psgd_geometry", []() {
+    int geo[11];
+    psgd_geometry(geo);
+    py::dict d;
+    const char* names[11] = {"threads", "max_rank", "slab", "tile_rows", "back_rows", "back_cols", "dense", "fold",
+                             "seg_bytes", "tile_bytes", "fold_bytes"};
+    for (int i = 0; i < 11; ++i) d[names[i]] = geo[i];
+    return d;
+  });
+  auto psgd_check = [](const char* who, int R, int ntiles, int nfolds, uintptr_t part, uintptr_t folds) {
+    if (R < 1 || R > 8) throw std::invalid_argument(std::string(who) + ": need 1 <= R <= 8");
+    if (ntiles < 0 || nfolds < 0) throw std::invalid_argument(std::string(who) + ": need ntiles >= 0 and nfolds >= 0");
+    if (nfolds > 0 && (!part || !folds)) throw std::invalid_argument(std::string(who) + ": folds need their table and the partial buffer");
+  };
+  m.def("psgd_qinit", [](uintptr_t st, uintptr_t q, long n, uint64_t key) {
+    if (n < 0) throw std::invalid_argument("psgd_qinit: need n >= 0");
+    if (n == 0) return;
+    if (!q || q % 16) throw std::invalid_argument("psgd_qinit: q must be a 16-byte aligned buffer");
+    launch_psgd_qinit(S(st), P<float>(q), n, key);
+    check_last("psgd_qinit");
+  }, py::arg("stream"), py::arg("q"), py::arg("n"), py::arg("key"));
+  m.def("psgd_project", [psgd_check](uintptr_t st, uintptr_t x, uintptr_t g, uintptr_t residual, uintptr_t segs,
+                                     uintptr_t tiles, int ntiles, uintptr_t q, int R, uintptr_t send, uintptr_t part,
+                                     uintptr_t folds, int nfolds) {
+    psgd_check("psgd_project", R, ntiles, nfolds, part, folds);
+    if (ntiles == 0) return;
+    if (!x || !g || !residual || !segs || !tiles || !q || !send) throw std::invalid_argument("psgd_project: null buffer");
+    if ((x | g | residual) % 16) throw std::invalid_argument("psgd_project: x, g and residual must be 16-byte aligned");
+    launch_psgd_project(S(st), P<const float>(x), P<const float>(g), P<float>(residual), P<const void>(segs),
+                        P<const void>(tiles), ntiles, P<const float>(q), R, P<float>(send), P<float>(part),
+                        P<const void>(folds), nfolds);
+    check_last("psgd_project");
+  }, py::arg("stream"), py::arg("x"), py::arg("g"), py::arg("residual"), py::arg("segs"), py::arg("tiles"),
+     py::arg("ntiles"), py::arg("q"), py::arg("R"), py::arg("send"), py::arg("part"), py::arg("folds"), py::arg("nfolds"));
+  m.def("psgd_orth", [](uintptr_t st, uintptr_t segs, int nseg, uintptr_t p, int R) {
+    if (R < 1 || R > 8) throw std::invalid_argument("psgd_orth: need 1 <= R <= 8");
+    if (nseg < 0) throw std::invalid_argument("psgd_orth: need nseg >= 0");
+    if (nseg == 0) return;
+    if (!segs || !p) throw std::invalid_argument("psgd_orth: null buffer");
+    launch_psgd_orth(S(st), P<const void>(segs), nseg, P<float>(p), R);
+    check_last("psgd_orth");
+  }, py::arg("stream"), py::arg("segs"), py::arg("nseg"), py::arg("p"), py::arg("R"));
+  m.def("psgd_backproject", [psgd_check](uintptr_t st, uintptr_t d, uintptr_t segs, uintptr_t tiles, int ntiles,
+                                         uintptr_t p, int R, uintptr_t q, uintptr_t part, uintptr_t folds, int nfolds) {
+    psgd_check("psgd_backproject", R, ntiles, nfolds, part, folds);
+    if (ntiles == 0) return;
+    if (!d || !segs || !tiles || !p || !q) throw std::invalid_argument("psgd_backproject: null buffer");
+    launch_psgd_backproject(S(st), P<const float>(d), P<const void>(segs), P<const void>(tiles), ntiles,
+                            P<const float>(p), R, P<float>(q), P<float>(part), P<const void>(folds), nfolds);
+    check_last("psgd_backproject");
+  }, py::arg("stream"), py::arg("d"), py::arg("segs"), py::arg("tiles"), py::arg("ntiles"), py::arg("p"), py::arg("R"),
+     py::arg("q"), py::arg("part"), py::arg("folds"), py::arg("nfolds"));
+  m.def("psgd_apply", [psgd_check](uintptr_t st, uintptr_t x, uintptr_t g, uintptr_t residual, uintptr_t segs,
+                                   uintptr_t tiles, int ntiles, uintptr_t p, uintptr_t q, uintptr_t send, int R) {
+    psgd_check("psgd_apply", R, ntiles, 0, 0, 0);
+    if (ntiles == 0) return;
+    if (!x || !g || !residual || !segs || !tiles || !p || !q || !send) throw std::invalid_argument("psgd_apply: null buffer");
+    if ((x | g | residual) % 16) throw std::invalid_argument("psgd_apply: x, g and residual must be 16-byte aligned");
+    launch_psgd_apply(S(st), P<float>(x), P<float>(g), P<float>(residual), P<const void>(segs), P<const void>(tiles),
+                      ntiles, P<const float>(p), P<const float>(q), P<const float>(send), R);
+    check_last("psgd_apply");
+  }, py::arg("stream"), py::arg("x"), py::arg("g"), py::arg("residual"), py::arg("segs"), py::arg("tiles"),
+     py::arg("ntiles"), py::arg("p"), py::arg("q"), py::arg("send"), py::arg("R"));
 }
 
 // the module name carries the build variant (fedmi/_build.py VARIANTS): -DFEDMI_MODULE=_fedmi_native_<v>

@@ -13,7 +13,7 @@
 // tree, dp_finish folds the partials the same way.  The grid is a function of k alone (flat_grid).  There are no atomics,
 // so the same inputs, key and draw give the same bits on every run.
 //
-// Noise.  Philox4x32-10 (Salmon et al. 2011), key = the client's 64-bit secret, counter = (block lo, block hi, draw lo,
+// Noise (philox.h).  Philox4x32-10 (Salmon et al. 2011), key = the client's 64-bit secret, counter = (block lo, block hi, draw lo,
 // draw hi) with block = i >> 2; entry i takes lane i & 3 of its block, on the vector path and on the tail alike.  The
 // four outputs r0..r3 give two Box-Muller pairs: u(r) = ((r >> 9) + 0.5) * 2^-23 is exact in fp32 and never 0 or 1;
 // lanes 0, 1 = sqrt(-2 ln u(r0)) * {cos, sin}(2 pi u(r1)), lanes 2, 3 the same from r2, r3.  The angle goes through
@@ -23,11 +23,14 @@
 // Cost per entry: 8 B read by dp_sumsq, 8 B read + 4 B written by the apply (4 B + 4 B when nothing is clipped,
 // nothing at all for clip-only with scale == 1), and a quarter of a Philox block and half a Box-Muller pair.
 #include "flat_map.h"
+#include "philox.h"
 
 namespace {
 
 using fedmi::flat_load;
 using fedmi::flat_store;
+using fedmi::Philox;
+using fedmi::box_muller;
 
 constexpr int DP_THREADS = 256;
 
@@ -80,45 +83,6 @@ __global__ __launch_bounds__(DP_THREADS) void dp_finish_kernel(const double* __r
     stats[1] = norm;
     stats[2] = (double)scale;
   }
-}
-
-struct Philox {
-  uint32_t k0, k1, d0, d1;   // key and draw, low word first
-
-  static FEDMI_DEV void round(uint32_t (&c)[4], uint32_t ka, uint32_t kb) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    c[0] = hi1 ^ c[1] ^ ka;
-    c[1] = lo1;
-    c[2] = hi0 ^ c[3] ^ kb;
-    c[3] = lo0;
-  }
-
-  // the four 32-bit outputs of one block
-  FEDMI_DEV void block(long blk, uint32_t (&c)[4]) const {
-    c[0] = (uint32_t)blk;
-    c[1] = (uint32_t)((unsigned long)blk >> 32);
-    c[2] = d0;
-    c[3] = d1;
-    uint32_t ka = k0, kb = k1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      round(c, ka, kb);
-      ka += 0x9E3779B9u;
-      kb += 0xBB67AE85u;
-    }
-  }
-};
-
-FEDMI_DEV float unit_open(uint32_t r) { return ((float)(r >> 9) + 0.5f) * 0x1p-23f; }
-
-// one Box-Muller pair from two 32-bit words: (radius * cos, radius * sin)
-FEDMI_DEV void box_muller(uint32_t ra, uint32_t rb, float& gc, float& gs) {
-  const float radius = sqrtf(-2.f * logf(unit_open(ra)));
-  float s, c;
-  sincospif(2.f * unit_open(rb), &s, &c);
-  gc = radius * c;
-  gs = radius * s;
 }
 
 template <bool NOISE>

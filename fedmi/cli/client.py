@@ -20,7 +20,7 @@ from ..engine import build_trainer
 from ..engine.base import TrainerConfig
 from ..engine.data import label_shard_indices, make_dataset
 from ..parallel.client_opt import add_client_opt_flags, make_client_opt
-from ..parallel.compress import make_compressor
+from ..parallel.compress import DEFAULT_POWERSGD_RANK, MAX_POWERSGD_RANK, make_compressor
 from ..parallel.dp import add_dp_flags, check_dp_flags, make_dp
 from ..parallel.fedavg import FedAvg
 from ..parallel.group import GroupManager
@@ -60,10 +60,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--noniid", type=int, default=0, help="label shards per client (0 = reference strided IID)")
     ap.add_argument("--client-index", type=int, default=0)
     ap.add_argument("--num-clients", type=int, default=1)
-    ap.add_argument("--compress", default=None, choices=["none", "topk", "int8"],
+    ap.add_argument("--compress", default=None, choices=["none", "topk", "int8", "powersgd"],
                     help="update compression (default with -c Y: int8 + error feedback, see "
-                         "fedmi.parallel.compress.DEFAULT_Y)")
+                         "fedmi.parallel.compress.DEFAULT_Y; powersgd: low-rank factors of the weight matrices, "
+                         "averaged by the plain all-reduce)")
     ap.add_argument("--topk-ratio", type=float, default=0.2)
+    ap.add_argument("--powersgd-rank", type=int, default=DEFAULT_POWERSGD_RANK,
+                    help=f"rank of --compress powersgd (1..{MAX_POWERSGD_RANK})")
     ap.add_argument("--compress-warmup", type=int, default=0, help="dense FedAvg rounds before -c Y compression starts")
     add_server_opt_flags(ap)
     add_client_opt_flags(ap)
@@ -98,6 +101,8 @@ def main(argv=None) -> int:
     check_dp_flags(a, ap.error)
     check_robust_flags(a, ap.error)
     check_secagg_flags(a, ap.error)
+    if not 1 <= a.powersgd_rank <= MAX_POWERSGD_RANK:
+        ap.error(f"--powersgd-rank must be in 1..{MAX_POWERSGD_RANK}")
     gzip = a.compressFlag == "Y"
     dev = pick_device(a.device)
     if dev.type == "cuda":
@@ -120,7 +125,7 @@ def main(argv=None) -> int:
         ap.error(f"--client-opt {a.client_opt} is not available for --model {a.model} on this engine: {e}"
                  + ("; FEDMI_TORCH_PATH=1 runs LeNet on the PyTorch engine, which has the hook"
                     if a.model.lower() == "lenet" else ""))
-    fedavg = FedAvg(compressor=make_compressor(comp_kind, a.topk_ratio, trainer, a.compress_warmup),
+    fedavg = FedAvg(compressor=make_compressor(comp_kind, a.topk_ratio, trainer, a.compress_warmup, a.powersgd_rank),
                     client_opt=client_opt,
                     dp=make_dp(a.dp_clip, trainer, a.dp_noise, a.dp_delta, a.dp_seed, who=a.address),
                     robust=make_robust(a.robust, trainer, a.robust_trim, a.robust_iters, a.robust_nu, a.robust_byz),

@@ -6,6 +6,11 @@ error-feedback delta + exact top-k (k = 1 % and 20 % of n, FEDMI_TOPK_RATIOS: th
 read+write pass over the state for scale ``rw_pass_us``), of the rank-ordered
 scatter of 4 ranks' payloads, of int8 quantisation and of a 4-rank dequant
 accumulate; plus payload bytes vs dense fp32.  One JSON line per size.
+
+The powersgd arm (csrc/kernels/powersgd.hip) runs on the real layouts of LeNet, ResNet-18 and MobileNet at the ranks of
+FEDMI_PSGD_RANKS (default 2,4): device time of each of the round's four launches and of the round without its two
+collectives, the bytes each moves (16 / 4 / 20 B per entry) over that time beside ``sgd_flat`` on the same state
+(20 B per entry), and the payload per round and client.  One JSON line per model and rank.
 """
 from __future__ import annotations
 
@@ -31,6 +36,69 @@ def _time(fn, iters):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / iters
+
+
+class _Layout:
+    """A trainer's float state with the model's state dict laid over it (what PowerSGDCompressor reads)."""
+
+    def __init__(self, model: str, dev):
+        from fedmi.models import build_model
+
+        shapes = [(k, tuple(v.shape)) for k, v in build_model(model).state_dict().items() if v.is_floating_point()]
+        sizes = [int(torch.Size(s).numel()) for _, s in shapes]
+        self.flat = torch.randn(sum(sizes), device=dev)
+        self.views, off = {}, 0
+        for (k, s), m in zip(shapes, sizes):
+            self.views[k] = self.flat[off:off + m].view(s)
+            off += m
+
+    def float_state(self):
+        return self.flat
+
+    def state_dict(self):
+        return self.views
+
+
+def powersgd_arm(nat, dev, S, out) -> None:
+    from fedmi.parallel.compress import PowerSGDCompressor
+
+    ranks = [int(v) for v in os.environ.get("FEDMI_PSGD_RANKS", "2,4").split(",")]
+    for model in os.environ.get("FEDMI_PSGD_MODELS", "lenet,resnet18,mobilenet").split(","):
+        tr = _Layout(model, dev)
+        n = tr.flat.numel()
+        iters = 200 if n < 1e6 else 20
+        grad, mom = torch.randn(n, device=dev) * 0.01, torch.zeros(n, device=dev)
+        t_sgd = _time(lambda: nat.sgd_flat(S(), tr.flat.data_ptr(), grad.data_ptr(), mom.data_ptr(), n, 0.01, 0.9, 5e-4,
+                                           0.0, False, False), iters)
+        for R in ranks:
+            c = PowerSGDCompressor(tr, rank=R)
+            x = tr.flat
+            x.copy_(c.global_ref).add_(grad)
+            t, k = c._tb, c._cnt
+            n_comp = sum(r * cl for _, r, cl in c.segments)
+            launches = {
+                "project": lambda: c.phase1(x),
+                "orth": lambda: nat.psgd_orth(S(), t["segs"].data_ptr(), k["segs"], c.send.data_ptr(), R),
+                "backproject": lambda: nat.psgd_backproject(
+                    S(), c.residual.data_ptr(), t["segs"].data_ptr(), t["backproject"].data_ptr(), k["backproject"],
+                    c.send.data_ptr(), R, c.q.data_ptr(), c.qpart.data_ptr(), t["qfolds"].data_ptr(), k["qfolds"]),
+                "apply": lambda: c.phase3(x, c.q),
+            }
+            c.phase2(c.phase1(x))                       # every timed launch starts from a finite, typical state
+            us = {name: _time(fn, iters) for name, fn in launches.items()}
+            c.residual.zero_()
+            t_round = _time(lambda: c.phase3(x, c.phase2(c.phase1(x))), iters)
+            moved = {"project": 16 * n_comp + 12 * c.n_dense, "backproject": 4 * n_comp, "apply": 20 * n}
+            rec = {"bench": "powersgd_kernels", "payload": model, "n": n, "rank": R, "segments": len(c.segments),
+                   "n_compressed": n_comp, "n_dense": c.n_dense, "tiles_project": k["project"],
+                   "tiles_backproject": k["backproject"], "folds": [k["pfolds"], k["qfolds"]],
+                   **{f"{name}_us": round(v, 2) for name, v in us.items()}, "round_us": round(t_round, 2),
+                   **{f"{name}_GBps": round(moved[name] / us[name] / 1e3, 1) for name in moved},
+                   "sgd_flat_us": round(t_sgd, 2), "sgd_flat_GBps": round(20 * n / t_sgd / 1e3, 1),
+                   "bytes_dense": 4 * n, "bytes_powersgd": c.payload_bytes,
+                   "ratio_powersgd": round(4 * n / c.payload_bytes, 1)}
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
 
 
 def main() -> int:
@@ -96,6 +164,7 @@ def main() -> int:
                "ratio_topk": round(4 * n / (8 * k), 2), "ratio_int8": round(4 * n / (n + 4 * nch), 2)}
         print(json.dumps(rec), flush=True)
         out.append(rec)
+    powersgd_arm(nat, dev, S, out)
     if len(sys.argv) > 1:
         Path(sys.argv[1]).write_text("".join(json.dumps(r) + "\n" for r in out))
     return 0
