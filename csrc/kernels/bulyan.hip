@@ -236,12 +236,10 @@ __global__ __launch_bounds__(kFoldThreads) void bulyan_cut_kernel(const long lon
   }
 }
 
-int* record_of(double* partial, long n) { return reinterpret_cast<int*>(partial + (long)krum_grid(n) * KR_TILE); }
-
 // launches 3 and 4 over the record that `partial` holds
 void launch_fold(hipStream_t st, const float* rows, long ld, int W, long n, int theta, int c, float* out,
                  double* partial, double* stats) {
-  const int* record = record_of(partial, n);
+  const int* record = gram_record(partial, n);
   long long* cuts = reinterpret_cast<long long*>(partial + (long)(krum_grid(n) + 1) * KR_TILE);
   const int grid = flat_grid(n);
   robust_dispatch(theta, [&](auto th) {
@@ -279,7 +277,7 @@ void launch_bulyan_fold(hipStream_t st, const float* rows, long ld, int W, long 
   if (n <= 0) return;
   BulyanRanks by_value{theta, {}};
   for (int s = 0; s < theta; ++s) by_value.rank[s] = ranks[s];
-  hipLaunchKernelGGL(bulyan_record_kernel, dim3(1), dim3(64), 0, st, by_value, record_of(partial, n));
+  hipLaunchKernelGGL(bulyan_record_kernel, dim3(1), dim3(64), 0, st, by_value, gram_record(partial, n));
   launch_fold(st, rows, ld, W, n, theta, c, out, partial, stats);
 }
 
@@ -292,7 +290,7 @@ void launch_bulyan(hipStream_t st, const float* rows, long ld, int W, long n, in
   bulyan_counts(W, byz, &f, &theta, &c);
   launch_gram_pass(st, rows, ld, W, n, partial);
   hipLaunchKernelGGL(bulyan_finish_kernel, dim3(1), dim3(kFoldThreads), 0, st, partial, krum_grid(n), krum_tile(W), W,
-                     f, theta, stats, record_of(partial, n));
+                     f, theta, stats, gram_record(partial, n));
   launch_fold(st, rows, ld, W, n, theta, c, out, partial, stats);
 }
 

@@ -219,7 +219,7 @@ void launch_krum(hipStream_t st, const float* rows, long ld, int W, long n, int 
   int k, m;
   krum_counts(W, byz, multi, &k, &m);
   const int grid = krum_grid(n);
-  int* record = reinterpret_cast<int*>(partial + (long)grid * KR_TILE);
+  int* record = gram_record(partial, n);
   launch_gram_pass(st, rows, ld, W, n, partial);
   hipLaunchKernelGGL(krum_finish_kernel, dim3(1), dim3(kFoldThreads), 0, st, partial, grid, krum_tile(W), W, k, m,
                      nullptr, stats, record);

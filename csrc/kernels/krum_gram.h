@@ -1,5 +1,5 @@
 // fedmi — what the rules built on the fp64 Gram pass share (krum.hip, bulyan.hip): the grid and tile rules, the fold of
-// the pass's partial tiles, and the launcher of the pass itself (the kernel lives in krum.hip).
+// the pass's partial tiles, the record's place, and the launcher of the pass itself (the kernel lives in krum.hip).
 #pragma once
 #include "robust_fold.h"
 
@@ -18,6 +18,9 @@ inline int krum_tile(int W) { return W <= 4 ? 4 : W <= 8 ? 8 : 16; }
 
 // partial[wg] = the workgroup's share of G = X X^T as krum_tile(W)^2 doubles, wg < krum_grid(n)  (krum.hip)
 void launch_gram_pass(hipStream_t st, const float* rows, long ld, int W, long n, double* partial);
+
+// the finish's record {count, the picked ranks ascending} (int32): the row of 256 doubles behind the pass's tiles
+inline int* gram_record(double* partial, long n) { return reinterpret_cast<int*>(partial + (long)krum_grid(n) * KR_TILE); }
 
 // fold_partial_rows' sibling for tiles: n_partial rows of E = P * P doubles (E = 16, 64 or 256); returns in lane t the
 // sum of entry t % E.  Lane (g, e), g = t / E, adds rows g, g + 1024 / E, .. in that order from 0, then a binary LDS

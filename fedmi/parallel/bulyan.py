@@ -36,15 +36,13 @@ SCAFFOLD's variate.
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 from typing import List, Tuple
 
 import torch
 
-from .. import native
-from .replicated import ReplicatedConfig
-from .robust import MAX_RANKS, GatheredAgg, sort_key
+from .krum import SelectAgg, SelectConfig, gram_select_torch, gram_torch
+from .robust import MAX_RANKS, sort_key
 
 KINDS = ("bulyan",)
 STATS_ROWS = 3 + MAX_RANKS
@@ -52,21 +50,10 @@ CUT_ROW = 2 + MAX_RANKS
 
 
 @dataclass
-class BulyanConfig(ReplicatedConfig):
+class BulyanConfig(SelectConfig):
     kind: str = "bulyan"
-    byz: int = 1                     # --robust-byz F: arbitrary clients to withstand
 
-    KINDS = KINDS
-    FIELDS = ("kind", "byz")
-    ROLE, FLAG = "robust aggregation", "--robust / --robust-byz"
-    MISMATCH_TAIL = ", or the clients select different peers and their models drift apart"
-
-    def __post_init__(self):
-        if self.kind not in KINDS:
-            raise ValueError(f"Bulyan aggregation: kind must be one of {KINDS}, not {self.kind!r}")
-        self.byz = int(self.byz)
-        if self.byz < 1:
-            raise ValueError("Bulyan aggregation: the Byzantine count F must be >= 1")
+    KINDS, RULE = KINDS, "Bulyan"
 
     def counts(self, world: int) -> Tuple[int, int, int, int]:
         return bulyan_counts(world, self.byz)
@@ -80,32 +67,8 @@ def bulyan_counts(world: int, byz: int) -> Tuple[int, int, int, int]:
 
 def bulyan_select_torch(G: torch.Tensor, byz: int) -> Tuple[torch.Tensor, List[int]]:
     """``stats[19, 16]`` (fp64, row 18 still 0) and the selected ranks, ascending, from the symmetric ``[W, W]`` Gram."""
-    W = G.shape[0]
-    f, theta, _, _ = bulyan_counts(W, byz)
-    g = G.tolist()
-    stats = torch.zeros((STATS_ROWS, MAX_RANKS), dtype=torch.float64)
-    d = [[0.0] * W for _ in range(W)]
-    for i in range(W):
-        for j in range(W):
-            if i != j:
-                v = (g[i][i] + g[j][j]) - 2.0 * g[i][j]
-                d[i][j] = (0.0 if v < 0.0 else v) if math.isfinite(v) else math.inf
-        stats[2 + i, :W] = torch.tensor(d[i], dtype=torch.float64)
-    alive = list(range(W))
-    for rnd in range(1, theta + 1):
-        k = max(1, len(alive) - f - 2)
-        score = {}
-        for i in alive:
-            near = sorted((d[i][j], j) for j in alive if j != i)[:k]
-            s = near[0][0] if near else 0.0
-            for v, _ in near[1:]:
-                s = s + v
-            score[i] = s
-            stats[0, i] = s
-        best = min(alive, key=lambda i: (score[i], i))
-        stats[1, best] = float(rnd)
-        alive.remove(best)
-    return stats, [r for r in range(W) if r not in alive]
+    f, theta, _, _ = bulyan_counts(G.shape[0], byz)
+    return gram_select_torch(G, f, theta, 1, STATS_ROWS)
 
 
 def bulyan_fold_torch(rows: torch.Tensor, c: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -138,51 +101,25 @@ def bulyan_fold_torch(rows: torch.Tensor, c: int) -> Tuple[torch.Tensor, torch.T
 def bulyan_torch(rows: torch.Tensor, byz: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """The kernels' twin in torch: ``rows`` is ``[W, n]`` fp32; returns ``(z[n] fp32, stats[19, 16] fp64)``.  The same
     formulas; the Gram's fp64 sums run in torch's order, not the kernels'."""
-    x = rows.double()
-    G = torch.triu(x @ x.T)
-    stats, selected = bulyan_select_torch((G + torch.triu(G, 1).T).cpu(), byz)
+    stats, selected = bulyan_select_torch(gram_torch(rows), byz)
     z, cut = bulyan_fold_torch(rows[selected], bulyan_counts(rows.shape[0], byz)[2])
     stats[CUT_ROW, selected] = cut.cpu().double()
     return z, stats
 
 
-class BulyanAgg(GatheredAgg):
-    """Bulyan in the ``robust`` slot of a :class:`fedmi.parallel.fedavg.FedAvg`, with
-    :class:`fedmi.parallel.robust.RobustAgg`'s interface; ``stats`` is ``[19][16]`` of the last call."""
+class BulyanAgg(SelectAgg):
+    """Bulyan; ``stats`` is ``[19][16]`` of the last call."""
 
-    def __init__(self, trainer, cfg: BulyanConfig):
-        self.stats = torch.zeros((STATS_ROWS, MAX_RANKS), dtype=torch.float64, device=trainer.float_state().device)
-        super().__init__(trainer, cfg, self.stats)
-        self._warned = False
+    STATS_ROWS = STATS_ROWS
+    BINDING, TWIN = "bulyan", staticmethod(bulyan_torch)
 
     def _run(self, x, W, fedavg):
-        if self.cfg.counts(W)[0] == 0 and not self._warned:
-            from ..utils.metrics import log
-
-            self._warned = True
-            log("robust", f"{W} clients: nothing can be withstood (F_eff = 0), --robust bulyan selects everyone and is "
-                          f"the plain mean until the federation has 7 or more")
+        if self.cfg.counts(W)[0] == 0:
+            self._log_once(f"{W} clients: nothing can be withstood (F_eff = 0), --robust bulyan selects everyone and is "
+                           f"the plain mean until the federation has 7 or more")
         return super()._run(x, W, fedavg)
 
-    def _reduce(self, rows, x, W, n):
-        if self._nat is not None:
-            # one allocation: the Gram tiles, the record and the cut rows, as rows of 256 doubles (16 of the shared
-            # [*, 16] buffer's rows each)
-            self._nat.bulyan(native.stream_handle(self.dev), rows.data_ptr(), rows.shape[1], W, n, self.cfg.byz,
-                             x.data_ptr(),
-                             self._partials(MAX_RANKS * self._nat.bulyan_partials(n), torch.float64).data_ptr(),
-                             self.stats.data_ptr())
-        else:
-            with torch.no_grad():
-                z, stats = bulyan_torch(rows[:, :n], self.cfg.byz)
-                x.copy_(z)
-                self.stats.copy_(stats)
-        return self.cfg.counts(W)[0], W
-
     def _decode(self, tag, stats) -> dict:
-        """``robust_byz`` (the effective one), ``robust_selected`` (the ranks folded), ``robust_score`` and
-        ``robust_cut`` (per client, the coordinates at which its value was dropped)."""
-        f_eff, W = tag
-        return {"robust_byz": f_eff, "robust_selected": [r for r in range(W) if float(stats[1, r]) > 0.0],
-                "robust_score": [float(v) for v in stats[0, :W].tolist()],
-                "robust_cut": [int(v) for v in stats[CUT_ROW, :W].tolist()]}
+        """:class:`fedmi.parallel.krum.SelectAgg`'s keys and ``robust_cut`` (per client, the coordinates at which its
+        value was dropped)."""
+        return {**super()._decode(tag, stats), "robust_cut": [int(v) for v in stats[CUT_ROW, :tag[1]].tolist()]}

@@ -113,6 +113,9 @@ class GeoMedAgg(GatheredAgg):
                 self.history[:, :, :W] = hist
         return W
 
+    def _raw(self, W):
+        return self.history[:, :, :W]
+
     def _decode(self, W, h) -> dict:
         """``robust_weight`` (the weights that formed the aggregate) and ``robust_dist`` (every client's distance to it)."""
         T = self.cfg.iters

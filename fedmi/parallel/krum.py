@@ -36,7 +36,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Tuple
+from typing import List, Tuple
 
 import torch
 
@@ -49,21 +49,30 @@ STATS_ROWS = 2 + MAX_RANKS
 
 
 @dataclass
-class KrumConfig(ReplicatedConfig):
-    kind: str = "krum"
+class SelectConfig(ReplicatedConfig):
+    """Base of the configs of the rules that select clients by Krum's scores; a subclass names its ``KINDS`` and its
+    ``RULE`` (the word in the messages) and supplies ``counts(world)``."""
+    kind: str
     byz: int = 1                     # --robust-byz F: arbitrary clients to withstand
 
-    KINDS = KINDS
+    RULE = ""
     FIELDS = ("kind", "byz")
     ROLE, FLAG = "robust aggregation", "--robust / --robust-byz"
     MISMATCH_TAIL = ", or the clients select different peers and their models drift apart"
 
     def __post_init__(self):
-        if self.kind not in KINDS:
-            raise ValueError(f"Krum aggregation: kind must be one of {KINDS}, not {self.kind!r}")
+        if self.kind not in self.KINDS:
+            raise ValueError(f"{self.RULE} aggregation: kind must be one of {self.KINDS}, not {self.kind!r}")
         self.byz = int(self.byz)
         if self.byz < 1:
-            raise ValueError("Krum aggregation: the Byzantine count F must be >= 1")
+            raise ValueError(f"{self.RULE} aggregation: the Byzantine count F must be >= 1")
+
+
+@dataclass
+class KrumConfig(SelectConfig):
+    kind: str = "krum"
+
+    KINDS, RULE = KINDS, "Krum"
 
     @property
     def multi(self) -> bool:
@@ -79,67 +88,107 @@ def krum_counts(world: int, byz: int, multi: bool) -> Tuple[int, int, int]:
     return f, max(1, world - f - 2), world - f if multi else 1
 
 
-def krum_finish_torch(G: torch.Tensor, byz: int, multi: bool) -> torch.Tensor:
-    """``stats[18, 16]`` (fp64) from the symmetric ``[W, W]`` Gram matrix."""
+def gram_torch(rows: torch.Tensor) -> torch.Tensor:
+    """The symmetric ``[W, W]`` fp64 Gram matrix of ``rows`` (``[W, n]`` fp32), on the CPU, read from its upper triangle
+    as the kernel reads it; the sums run in torch's order, not the kernels'."""
+    x = rows.double()
+    G = torch.triu(x @ x.T)
+    return (G + torch.triu(G, 1).T).cpu()
+
+
+def gram_select_torch(G: torch.Tensor, f: int, rounds: int, picks: int,
+                      stats_rows: int = STATS_ROWS) -> Tuple[torch.Tensor, List[int]]:
+    """The loop of both finish kernels (``krum_finish``: one round of ``m`` picks; ``bulyan_finish``: ``theta`` rounds of
+    one): from the symmetric ``[W, W]`` Gram matrix, ``rounds`` rounds over the alive set that pick the ``picks``
+    clients of lowest ``(score, rank)`` each, with ``F_eff = f``.  Returns ``stats[stats_rows,
+    16]`` (fp64: row 0 the score in the client's last round alive, row 1 the round in which it was picked, rows 2..17
+    ``d``, any further row 0) and the picked ranks, ascending."""
     W = G.shape[0]
-    _, k, m = krum_counts(W, byz, multi)
     g = G.tolist()
-    stats = torch.zeros((STATS_ROWS, MAX_RANKS), dtype=torch.float64)
-    score = []
+    stats = torch.zeros((stats_rows, MAX_RANKS), dtype=torch.float64)
+    d = [[0.0] * W for _ in range(W)]
     for i in range(W):
-        d = []
         for j in range(W):
-            v = 0.0 if i == j else (g[i][i] + g[j][j]) - 2.0 * g[i][j]
-            d.append((0.0 if v < 0.0 else v) if math.isfinite(v) else math.inf)
-        stats[2 + i, :W] = torch.tensor(d, dtype=torch.float64)
-        near = sorted((d[j], j) for j in range(W) if j != i)[:k]
-        s = near[0][0]
-        for v, _ in near[1:]:
-            s = s + v
-        score.append(s)
-    stats[0, :W] = torch.tensor(score, dtype=torch.float64)
-    for _, r in sorted((score[r], r) for r in range(W))[:m]:
-        stats[1, r] = 1.0
-    return stats
+            if i != j:
+                v = (g[i][i] + g[j][j]) - 2.0 * g[i][j]
+                d[i][j] = (0.0 if v < 0.0 else v) if math.isfinite(v) else math.inf
+        stats[2 + i, :W] = torch.tensor(d[i], dtype=torch.float64)
+    alive = list(range(W))
+    for rnd in range(1, rounds + 1):
+        k = max(1, len(alive) - f - 2)
+        score = {}
+        for i in alive:
+            near = sorted((d[i][j], j) for j in alive if j != i)[:k]
+            s = near[0][0] if near else 0.0
+            for v, _ in near[1:]:
+                s = s + v
+            score[i] = s
+            stats[0, i] = s
+        for i in sorted(alive, key=lambda i: (score[i], i))[:picks]:
+            stats[1, i] = float(rnd)
+            alive.remove(i)
+    return stats, [r for r in range(W) if r not in alive]
+
+
+def krum_finish_torch(G: torch.Tensor, byz: int, multi: bool) -> torch.Tensor:
+    """``stats[18, 16]`` (fp64) from the symmetric ``[W, W]`` Gram matrix: one round of ``m`` picks."""
+    f, _, m = krum_counts(G.shape[0], byz, multi)
+    return gram_select_torch(G, f, 1, m)[0]
 
 
 def krum_torch(rows: torch.Tensor, byz: int, multi: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     """The kernels' twin in torch: ``rows`` is ``[W, n]`` fp32; returns ``(z[n] fp32, stats[18, 16] fp64)``.  The same
     formulas; the Gram's fp64 sums run in torch's order, not the kernels'."""
-    x = rows.double()
-    G = torch.triu(x @ x.T)
-    stats = krum_finish_torch((G + torch.triu(G, 1).T).cpu(), byz, multi)
-    chosen = [r for r in range(rows.shape[0]) if float(stats[1, r]) == 1.0]
+    f, _, m = krum_counts(rows.shape[0], byz, multi)
+    stats, chosen = gram_select_torch(gram_torch(rows), f, 1, m)
     z = rows[chosen[0]].clone()
     for r in chosen[1:]:
         z = z + rows[r]
     return z / torch.tensor(float(len(chosen)), dtype=torch.float32, device=rows.device), stats
 
 
-class KrumAgg(GatheredAgg):
-    """The Krum rules in the ``robust`` slot of a :class:`fedmi.parallel.fedavg.FedAvg`, with
-    :class:`fedmi.parallel.robust.RobustAgg`'s interface; ``stats`` is ``[18][16]`` of the last call."""
+class SelectAgg(GatheredAgg):
+    """Base of the rules built on the Gram pass and Krum's selection, in the ``robust`` slot of a
+    :class:`fedmi.parallel.fedavg.FedAvg` with :class:`fedmi.parallel.robust.RobustAgg`'s interface; ``stats`` is
+    ``[STATS_ROWS][16]`` (fp64) of the last call.  A subclass names its ``BINDING`` (``<BINDING>_partials(n)`` sizes its
+    scratch) and its ``TWIN`` in torch; both take the rows and then :meth:`_rule_args`."""
 
-    def __init__(self, trainer, cfg: KrumConfig):
-        self.stats = torch.zeros((STATS_ROWS, MAX_RANKS), dtype=torch.float64, device=trainer.float_state().device)
+    STATS_ROWS = STATS_ROWS
+    BINDING, TWIN = "", None
+
+    def __init__(self, trainer, cfg: SelectConfig):
+        self.stats = torch.zeros((self.STATS_ROWS, MAX_RANKS), dtype=torch.float64,
+                                 device=trainer.float_state().device)
         super().__init__(trainer, cfg, self.stats)
+
+    def _rule_args(self) -> tuple:
+        return (self.cfg.byz,)
 
     def _reduce(self, rows, x, W, n):
         if self._nat is not None:
-            # the partials are rows of 256 doubles: 16 rows of the shared [*, 16] buffer each
-            self._nat.krum(native.stream_handle(self.dev), rows.data_ptr(), rows.shape[1], W, n, self.cfg.byz,
-                           self.cfg.multi, x.data_ptr(),
-                           self._partials(MAX_RANKS * self._nat.krum_partials(n), torch.float64).data_ptr(),
-                           self.stats.data_ptr())
+            # one allocation; the partials are rows of 256 doubles: 16 rows of the shared [*, 16] buffer each
+            blocks = MAX_RANKS * getattr(self._nat, self.BINDING + "_partials")(n)
+            getattr(self._nat, self.BINDING)(native.stream_handle(self.dev), rows.data_ptr(), rows.shape[1], W, n,
+                                             *self._rule_args(), x.data_ptr(),
+                                             self._partials(blocks, torch.float64).data_ptr(), self.stats.data_ptr())
         else:
             with torch.no_grad():
-                z, stats = krum_torch(rows[:, :n], self.cfg.byz, self.cfg.multi)
+                z, stats = self.TWIN(rows[:, :n], *self._rule_args())
                 x.copy_(z)
                 self.stats.copy_(stats)
         return self.cfg.counts(W)[0], W
 
     def _decode(self, tag, stats) -> dict:
-        """``robust_byz`` (the effective one), ``robust_selected`` (the ranks kept) and ``robust_score``."""
+        """``robust_byz`` (the effective one), ``robust_selected`` (the ranks picked) and ``robust_score``."""
         f_eff, W = tag
-        return {"robust_byz": f_eff, "robust_selected": [r for r in range(W) if float(stats[1, r]) == 1.0],
+        return {"robust_byz": f_eff, "robust_selected": [r for r in range(W) if float(stats[1, r]) > 0.0],
                 "robust_score": [float(v) for v in stats[0, :W].tolist()]}
+
+
+class KrumAgg(SelectAgg):
+    """The Krum rules; ``stats`` is ``[18][16]`` of the last call."""
+
+    BINDING, TWIN = "krum", staticmethod(krum_torch)
+
+    def _rule_args(self) -> tuple:
+        return self.cfg.byz, self.cfg.multi

@@ -105,6 +105,15 @@ class GatheredAgg(ReplicatedState):
         self._partial = None             # [blocks, 16], one row per workgroup of the sweep
         self._mirror = HostMirror(stats)
         self._seen = {}                  # the decoded statistics of the newest call known on the host
+        self._logged = False
+
+    def _log_once(self, text: str) -> None:
+        """``text`` to the log, the first time only (a federation too small for the rule says so once, not per round)."""
+        if not self._logged:
+            from ..utils.metrics import log
+
+            self._logged = True
+            log("robust", text)
 
     def _rolled(self) -> List[torch.Tensor]:
         return []
@@ -136,17 +145,42 @@ class GatheredAgg(ReplicatedState):
         """Gather and reduce; returns what :meth:`_decode` needs besides the statistics."""
         return self._reduce(self._gather(x, W, fedavg), x, W, x.numel())
 
-    def _gather(self, x: torch.Tensor, W: int, fedavg) -> torch.Tensor:
-        n = x.numel()
+    def stack(self, states) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The rule over clients simulated in one process (tools/fedavg_sim.py): ``states`` is a list of equal-length
+        fp32 tensors, client ``r``'s in place ``r``.  Fills the gather buffer as the collective would, runs
+        :meth:`_reduce` and posts the statistics as :meth:`aggregate` does.  Returns the aggregate (a new tensor) and
+        :meth:`_raw`, the device statistics of this call: the rule's own buffer or a view of it, which the next call
+        overwrites (clone it to keep it)."""
+        W, n = len(states), states[0].numel()
+        if W > MAX_RANKS:
+            raise ValueError(f"robust aggregation handles at most {MAX_RANKS} clients, the federation has {W}")
+        rows = self._buffer(W, n)
+        for r, x in enumerate(states):
+            rows[r, :n].copy_(x)
+        out = torch.empty(n, dtype=torch.float32, device=self.dev)
+        self._collect()
+        self._mirror.post(self._reduce(rows, out, W, n))
+        return out, self._raw(W)
+
+    def _raw(self, W: int) -> torch.Tensor:
+        """The statistics tensor as the rule's kernels leave it (a subclass cuts it to ``W`` clients where it can)."""
+        return self._mirror.stats
+
+    def _buffer(self, W: int, n: int) -> torch.Tensor:
         ld = (n + 3) & ~3                           # every row 16-byte aligned
         if self._rows is None or tuple(self._rows.shape) != (W, ld):
             self._rows = None                       # (the old one first: ResNet-18 at 8 clients is 358 MB)
             self._rows = torch.zeros((W, ld), dtype=torch.float32, device=self.dev)
-        if fedavg.transport is not None:
-            self._rows[:, :n].copy_(fedavg.transport.all_gather(x))
-        else:
-            self._all_gather([self._rows[r, :n] for r in range(W)], x, fedavg.group, fedavg.abort)
         return self._rows
+
+    def _gather(self, x: torch.Tensor, W: int, fedavg) -> torch.Tensor:
+        n = x.numel()
+        rows = self._buffer(W, n)
+        if fedavg.transport is not None:
+            rows[:, :n].copy_(fedavg.transport.all_gather(x))
+        else:
+            self._all_gather([rows[r, :n] for r in range(W)], x, fedavg.group, fedavg.abort)
+        return rows
 
     @staticmethod
     def _all_gather(rows, x, group, abort) -> None:
@@ -180,16 +214,12 @@ class RobustAgg(GatheredAgg):
     def __init__(self, trainer, cfg: RobustConfig):
         self.stats = torch.zeros(MAX_RANKS, dtype=torch.int64, device=trainer.float_state().device)
         super().__init__(trainer, cfg, self.stats)
-        self._warned = False
 
     def _run(self, x, W, fedavg):
         b = self.cfg.b_eff(W)
-        if b == 0 and not self._warned:
-            from ..utils.metrics import log
-
-            self._warned = True
-            log("robust", f"{W} clients: nothing can be trimmed (b_eff = 0), --robust {self.cfg.kind} is the plain "
-                          f"mean until the federation has 3 or more")
+        if b == 0:
+            self._log_once(f"{W} clients: nothing can be trimmed (b_eff = 0), --robust {self.cfg.kind} is the plain "
+                           f"mean until the federation has 3 or more")
         if fedavg.transport is None:
             return super()._run(x, W, fedavg)
         # the peer transport folds in its one-shot all-reduce: one kernel, no gather buffer
@@ -208,6 +238,9 @@ class RobustAgg(GatheredAgg):
                 x.copy_(out)
                 self.stats[:W] = cut
         return b, W
+
+    def _raw(self, W):
+        return self.stats[:W]
 
     def _decode(self, tag, stats) -> dict:
         """``robust_trim`` (the effective one) and ``robust_cut`` (one count per client)."""
@@ -237,6 +270,12 @@ def add_robust_flags(ap) -> None:
                          "count, and twice as many clients are left out and values cut per coordinate")
 
 
+def compression_on(a) -> bool:
+    """Whether the parsed flags ask for compressed updates: ``--compress`` where the parser has it, else ``-c Y``."""
+    compress = getattr(a, "compress", None)
+    return compress != "none" if compress is not None else getattr(a, "compressFlag", None) == "Y"
+
+
 def check_robust_flags(a, error) -> None:
     """The flag combinations a robust rule cannot serve, each refused through ``error`` (``ArgumentParser.error``)."""
     if getattr(a, "robust", "none") == "none":
@@ -252,8 +291,7 @@ def check_robust_flags(a, error) -> None:
     if getattr(a, "agg", "collective") == "grpc":
         error("--robust needs --agg collective: with --agg grpc the coordinator averages the clients' models "
               "(reference peers), nothing folds them robustly")
-    compress = getattr(a, "compress", None)
-    if (compress is not None and compress != "none") or (compress is None and getattr(a, "compressFlag", None) == "Y"):
+    if compression_on(a):
         error("--robust cannot be combined with compression (-c Y / --compress): the compressors aggregate sums of "
               "quantised deltas, not the clients' models")
     if getattr(a, "client_opt", "none") == "scaffold":

@@ -48,7 +48,7 @@ import torch
 
 from .. import native
 from .replicated import ReplicatedConfig
-from .robust import MAX_RANKS, GatheredAgg
+from .robust import MAX_RANKS, GatheredAgg, compression_on
 
 KINDS = ("pairwise",)
 Q_MAX = (1 << 27) - 1
@@ -341,8 +341,7 @@ def check_secagg_flags(a, error) -> None:
     if getattr(a, "agg", "collective") == "grpc":
         error("--secagg needs --agg collective: with --agg grpc the coordinator receives and averages the clients' "
               "raw models (reference peers), nothing masks them")
-    compress = getattr(a, "compress", None)
-    if (compress is not None and compress != "none") or (compress is None and getattr(a, "compressFlag", None) == "Y"):
+    if compression_on(a):
         error("--secagg cannot be combined with compression (-c Y / --compress): the compressors send quantised "
               "deltas of their own, which the masks do not cover")
     if getattr(a, "robust", "none") != "none":

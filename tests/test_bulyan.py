@@ -9,8 +9,10 @@ import torch
 
 from fedmi.parallel.bulyan import (BulyanAgg, BulyanConfig, bulyan_counts, bulyan_fold_torch, bulyan_select_torch,
                                    bulyan_torch)
+from fedmi.parallel.krum import gram_select_torch
 from fedmi.parallel.robust import GatheredAgg, make_robust
 from tests import bulyan_check as bc
+from tests import krum_check as kc
 from tests.robust_check import same_bits
 from tests.test_robust import _sim, _Stub
 
@@ -29,6 +31,27 @@ def test_twin_matches_reference_bit_for_bit(W, n):
     out, ref, _ = bc.reference(rows, G, 3)
     assert z.numpy().tobytes() == out.tobytes() and stats.numpy()[[1, 18]].tobytes() == ref[[1, 18]].tobytes()
     assert not set(sel) & set(range(W - f, W))                           # no attacker is selected
+
+
+@pytest.mark.parametrize("W", [2, 3, 7, 9, 16])
+@pytest.mark.parametrize("F", [1, 3])
+def test_one_selection_loop_is_both_rules(W, F):
+    """The shared loop with Krum's counts (one round of m picks) and with Bulyan's (theta rounds of one) equals either
+    rule's own reference: stats bytes and picked ranks; a tail alone, a long row, and a long row with one NaN client."""
+    for n, nan_client in ((1, None), (1027, None), (1027, W // 2)):
+        rows = bc.inputs(W, n).copy()
+        if nan_client is not None:
+            rows[nan_client] = np.nan
+        G = bc.gram(rows)
+        for multi in (False, True):
+            f, _, m = kc.counts(W, F, multi)
+            want, want_sel = kc.finish(G, W, F, multi)
+            got, sel = gram_select_torch(torch.from_numpy(G), f, 1, m)
+            assert got.numpy().tobytes() == want.tobytes() and sel == want_sel and len(sel) == m
+        f, theta, _, _ = bc.counts(W, F)
+        want, want_sel, _ = bc.select(G, W, F)
+        got, sel = gram_select_torch(torch.from_numpy(G), f, theta, 1, 19)
+        assert got.numpy().tobytes() == want.tobytes() and sel == want_sel and len(sel) == theta
 
 
 @pytest.mark.parametrize("theta,c", [(2, 0), (3, 2), (5, 4), (8, 2), (9, 6), (16, 6)])

@@ -8,6 +8,7 @@ import torch
 from fedmi import native
 from fedmi.parallel.robust import GatheredAgg, make_robust
 from tests import bulyan_check as bc
+from tests import krum_check as kc
 from tests.robust_check import same_bits
 from tests.test_robust_gpu import _FakeFedAvg, _GpuStub
 
@@ -65,6 +66,37 @@ def test_selection_bit_for_bit(nat, gpu_device, W, F, n):
     _, stats, record = _run(nat, gpu_device, rows, F)
     want, selected, _ = bc.select(_run(nat, gpu_device, rows)[:W, :W], W, F)
     assert stats[:18].tobytes() == want[:18].tobytes() and record == selected == ref_selected and len(record) == theta
+
+
+@pytest.mark.parametrize("W", [9, 16])
+@pytest.mark.parametrize("F", [1, 3])
+def test_selection_when_every_score_ties(nat, gpu_device, W, F):
+    """All W rows are one row: every distance and so every score is the same number, and the rank alone decides --
+    several picks in ONE round (krum, multikrum) and one pick in each of many rounds (bulyan).  Stats rows 0 .. 17 and
+    the record equal the references applied to the kernel's own G; the picked are the lowest ranks; Bulyan's round
+    numbers count up in rank order."""
+    n = 5
+    rows = torch.randn(n, generator=torch.Generator().manual_seed(W)).repeat(W, 1).numpy()
+    G = _run(nat, gpu_device, rows)[:W, :W]
+    padded = torch.zeros((W, 8), dtype=torch.float32, device=gpu_device)
+    padded[:, :n].copy_(torch.from_numpy(rows))
+    for multi in (False, True):
+        partial = torch.zeros((nat.krum_partials(n), 256), dtype=torch.float64, device=gpu_device)
+        out = torch.empty(8, dtype=torch.float32, device=gpu_device)
+        res = torch.full((18, 16), CANARY, dtype=torch.float64, device=gpu_device)
+        nat.krum(native.stream_handle(), padded.data_ptr(), 8, W, n, F, multi, out.data_ptr(), partial.data_ptr(),
+                 res.data_ptr())
+        torch.cuda.synchronize()
+        rec = partial[-1].cpu().view(torch.int32)[:17].tolist()
+        want, selected = kc.finish(G, W, F, multi)
+        assert res.cpu().numpy().tobytes() == want.tobytes()
+        assert rec[1:1 + rec[0]] == selected == list(range(kc.counts(W, F, multi)[2]))
+        assert out[:n].cpu().numpy().tobytes() == kc.select(rows, selected).tobytes()
+    theta = bc.counts(W, F)[1]
+    _, stats, record = _run(nat, gpu_device, rows, F)
+    want, selected, _ = bc.select(G, W, F)
+    assert stats[:18].tobytes() == want[:18].tobytes() and record == selected == list(range(theta))
+    assert stats[1].tolist() == [float(r + 1) for r in range(theta)] + [0.0] * (16 - theta)
 
 
 @pytest.mark.parametrize("theta", [2, 3, 5, 8, 9, 14, 16])

@@ -42,102 +42,10 @@ def attack_state(kind: str, start: torch.Tensor, x: torch.Tensor, scale: float) 
 
 
 def robust_stack(robust, states, nat=None):
-    """The robust aggregate of the simulated clients' float states (a list of equal-length fp32 tensors) and the cut
-    counts: ``robust_reduce`` (csrc/kernels/robust.hip) on a GPU, its torch twin elsewhere."""
-    from fedmi import native
-    from fedmi.parallel.robust import robust_reduce_torch
-
-    W, n = len(states), states[0].numel()
-    if robust.cfg.kind == "geomed":
-        return geomed_stack(robust, states, nat)
-    if robust.cfg.kind in ("krum", "multikrum"):
-        return krum_stack(robust, states, nat)
-    if robust.cfg.kind == "bulyan":
-        return bulyan_stack(robust, states, nat)
-    b = robust.cfg.b_eff(W)
-    if not states[0].is_cuda:
-        return robust_reduce_torch(torch.stack(states), b)
-    nat = nat or native.require()
-    dev = states[0].device
-    ld = (n + 3) & ~3
-    rows = torch.zeros((W, ld), dtype=torch.float32, device=dev)
-    for r, x in enumerate(states):
-        rows[r, :n].copy_(x)
-    out = torch.empty(n, dtype=torch.float32, device=dev)
-    partial = torch.zeros((max(1, nat.robust_partials(n)), 16), dtype=torch.int64, device=dev)
-    stats = torch.zeros(16, dtype=torch.int64, device=dev)
-    nat.robust_reduce(native.stream_handle(dev), rows.data_ptr(), ld, W, n, b, out.data_ptr(), partial.data_ptr(),
-                      stats.data_ptr())
-    return out, stats[:W]
-
-
-def geomed_stack(robust, states, nat=None):
-    """The geometric-median aggregate of the simulated clients' float states and its history ``[T + 1, 3, W]``
-    (sumsq, dist, w per pass): ``geomed`` (csrc/kernels/geomed.hip) on a GPU, its torch twin elsewhere."""
-    from fedmi import native
-    from fedmi.parallel.geomed import geomed_torch
-
-    W, n, T = len(states), states[0].numel(), robust.cfg.iters
-    if not states[0].is_cuda:
-        return geomed_torch(torch.stack(states), T, robust.cfg.nu)
-    nat = nat or native.require()
-    dev = states[0].device
-    ld = (n + 3) & ~3
-    rows = torch.zeros((W, ld), dtype=torch.float32, device=dev)
-    for r, x in enumerate(states):
-        rows[r, :n].copy_(x)
-    out = torch.empty(n, dtype=torch.float32, device=dev)
-    partial = torch.zeros((max(1, nat.geomed_partials(n)), 16), dtype=torch.float64, device=dev)
-    history = torch.zeros((T + 1, 3, 16), dtype=torch.float64, device=dev)
-    nat.geomed(native.stream_handle(dev), rows.data_ptr(), ld, W, n, T, robust.cfg.nu, out.data_ptr(),
-               partial.data_ptr(), history.data_ptr())
-    return out, history[:, :, :W]
-
-
-def krum_stack(robust, states, nat=None):
-    """The Krum / multi-Krum aggregate of the simulated clients' float states and its stats ``[18, 16]`` (score,
-    selected, the squared distances): ``krum`` (csrc/kernels/krum.hip) on a GPU, its torch twin elsewhere."""
-    from fedmi import native
-    from fedmi.parallel.krum import STATS_ROWS, krum_torch
-
-    W, n, cfg = len(states), states[0].numel(), robust.cfg
-    if not states[0].is_cuda:
-        return krum_torch(torch.stack(states), cfg.byz, cfg.multi)
-    nat = nat or native.require()
-    dev = states[0].device
-    ld = (n + 3) & ~3
-    rows = torch.zeros((W, ld), dtype=torch.float32, device=dev)
-    for r, x in enumerate(states):
-        rows[r, :n].copy_(x)
-    out = torch.empty(n, dtype=torch.float32, device=dev)
-    partial = torch.zeros((max(1, nat.krum_partials(n)), 256), dtype=torch.float64, device=dev)
-    stats = torch.zeros((STATS_ROWS, 16), dtype=torch.float64, device=dev)
-    nat.krum(native.stream_handle(dev), rows.data_ptr(), ld, W, n, cfg.byz, cfg.multi, out.data_ptr(),
-             partial.data_ptr(), stats.data_ptr())
-    return out, stats
-
-
-def bulyan_stack(robust, states, nat=None):
-    """The Bulyan aggregate of the simulated clients' float states and its stats ``[19, 16]`` (score, round picked,
-    the squared distances, the cut counts): ``bulyan`` (csrc/kernels/bulyan.hip) on a GPU, its torch twin elsewhere."""
-    from fedmi import native
-    from fedmi.parallel.bulyan import STATS_ROWS, bulyan_torch
-
-    W, n, cfg = len(states), states[0].numel(), robust.cfg
-    if not states[0].is_cuda:
-        return bulyan_torch(torch.stack(states), cfg.byz)
-    nat = nat or native.require()
-    dev = states[0].device
-    ld = (n + 3) & ~3
-    rows = torch.zeros((W, ld), dtype=torch.float32, device=dev)
-    for r, x in enumerate(states):
-        rows[r, :n].copy_(x)
-    out = torch.empty(n, dtype=torch.float32, device=dev)
-    partial = torch.zeros((max(1, nat.bulyan_partials(n)), 256), dtype=torch.float64, device=dev)
-    stats = torch.zeros((STATS_ROWS, 16), dtype=torch.float64, device=dev)
-    nat.bulyan(native.stream_handle(dev), rows.data_ptr(), ld, W, n, cfg.byz, out.data_ptr(), partial.data_ptr(),
-               stats.data_ptr())
-    return out, stats
+    """The robust aggregate of the simulated clients' float states (a list of equal-length fp32 tensors) and the rule's
+    raw statistics (the cut counts, the history or the stats): :meth:`fedmi.parallel.robust.GatheredAgg.stack`, the
+    rule's own kernels on a GPU and its torch twin elsewhere.  ``nat`` is ignored: the rule holds its native module."""
+    return robust.stack(states)
 
 
 def _eval_batch_bn(tr) -> None:
@@ -224,9 +132,8 @@ def _run_seed(a, seed, data, dev, out) -> None:
                     dp.privatize(tr, W)
             for tr in clients[W - a.attackers:] if a.attack != "none" else ():
                 tr.float_state().copy_(attack_state(a.attack, start, tr.float_state(), a.attack_scale))
-            cut = None
             if robust is not None and W > 1:
-                mean, cut = robust_stack(robust, [tr.float_state() for tr in clients])
+                mean, _ = robust_stack(robust, [tr.float_state() for tr in clients])
             elif sas[0] is not None and W > 1:
                 mean = secagg_stack(sas, [tr.float_state() for tr in clients])
             else:
@@ -273,26 +180,9 @@ def _run_seed(a, seed, data, dev, out) -> None:
             rec.update(dp_clip=a.dp_clip, dp_noise=a.dp_noise, dp_delta=a.dp_delta, dp_epsilon=rows[0]["dp_epsilon"],
                        dp_norm=[round(r.get("dp_norm", -1.0), 4) for r in rows],
                        dp_scale=[round(r.get("dp_scale", -1.0), 4) for r in rows])
-        if robust is not None and a.robust == "geomed":
-            # cut is the history here: the weights that formed the aggregate, the distances to it
-            T = robust.cfg.iters
-            rec.update(robust_kind=a.robust, robust_iters=T,
-                       robust_weight=cut[T - 1, 2].tolist() if cut is not None else None,
-                       robust_dist=cut[T, 1].tolist() if cut is not None else None)
-        elif robust is not None and a.robust in ("krum", "multikrum"):
-            # cut is the stats here: the scores and the selection
-            rec.update(robust_kind=a.robust, robust_byz=robust.cfg.counts(W)[0],
-                       robust_selected=[r for r in range(W) if float(cut[1, r]) == 1.0] if cut is not None else None,
-                       robust_score=cut[0, :W].tolist() if cut is not None else None)
-        elif robust is not None and a.robust == "bulyan":
-            # cut is the stats here: the scores, the rounds of the selection and the cut counts
-            rec.update(robust_kind=a.robust, robust_byz=robust.cfg.counts(W)[0],
-                       robust_selected=[r for r in range(W) if float(cut[1, r]) > 0.0] if cut is not None else None,
-                       robust_score=cut[0, :W].tolist() if cut is not None else None,
-                       robust_cut=[int(v) for v in cut[18, :W].tolist()] if cut is not None else None)
-        elif robust is not None:
-            rec.update(robust_kind=a.robust, robust_trim=robust.cfg.b_eff(W),
-                       robust_cut=cut.tolist() if cut is not None else None)
+        if robust is not None:
+            # the rule posted its statistics behind its kernels and the eval above synchronised: they are this round's
+            rec.update(robust.round_stats())
         if sas[0] is not None:
             sas[0]._mirror.post()                       # the eval above synchronised: this round's count is there
             rec.update(secagg_range=a.secagg_range, **sas[0].round_stats())
