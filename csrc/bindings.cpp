@@ -49,6 +49,9 @@ void launch_krum(hipStream_t, const float*, long, int, long, int, bool, float*, 
 int bulyan_partials(long);
 void launch_bulyan(hipStream_t, const float*, long, int, long, int, float*, double*, double*);
 void launch_bulyan_fold(hipStream_t, const float*, long, int, long, const int*, int, int, float*, double*, double*);
+int dnc_partials(long);
+void launch_dnc_gram(hipStream_t, const float*, long, int, long, double*, double*);
+void launch_dnc(hipStream_t, const float*, long, int, long, int, float*, double*, double*);
 int secagg_partials(long);
 void launch_secagg_mask(hipStream_t, const float*, const float*, const uint32_t*, int, int, uint64_t, long, int,
                         uint32_t*, long long*, long long*);
@@ -380,6 +383,34 @@ static void fedmi_bind(py::module_& m) {
     check_last("bulyan_fold");
   }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("record"), py::arg("c"),
      py::arg("out"), py::arg("partial"), py::arg("stats"));
+
+  // Divide-and-Conquer aggregation (csrc/kernels/dnc.hip): every client is scored by its squared projection on the top
+  // principal direction of the centred rows, read off the centred fp64 Gram matrix; out = the fp32 mean of the W - F_eff
+  // clients of lowest score, F_eff = max(0, min(byz, (W - 1) / 2)).  partial: dnc_partials(n) x 256 doubles of scratch;
+  // stats: 18 x 16 doubles = score, selected (1.0 / 0.0) and the 16 x 16 double-centred Gram.
+  m.def("dnc_partials", [](long n) {
+    if (n < 0) throw std::invalid_argument("dnc_partials: need n >= 0");
+    return dnc_partials(n);
+  });
+  m.def("dnc", [rows_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, int byz, uintptr_t out,
+                            uintptr_t partial, uintptr_t stats) {
+    rows_check("dnc", rows, ld, W, n, out, partial, stats);
+    if (byz < 0) throw std::invalid_argument("dnc: need byz >= 0");
+    if (n == 0) return;
+    launch_dnc(S(st), P<const float>(rows), ld, W, n, byz, P<float>(out), P<double>(partial), P<double>(stats));
+    check_last("dnc");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("byz"), py::arg("out"),
+     py::arg("partial"), py::arg("stats"));
+  // the centred Gram pass and its fold alone: gram = G = Y Y^T, y = x - the column pivot, as 16 x 16 doubles, 0 outside
+  // W x W (nothing else is written)
+  m.def("dnc_gram", [rows_check](uintptr_t st, uintptr_t rows, long ld, int W, long n, uintptr_t partial,
+                                 uintptr_t gram) {
+    rows_check("dnc_gram", rows, ld, W, n, gram, partial, gram);
+    if (n == 0) return;
+    launch_dnc_gram(S(st), P<const float>(rows), ld, W, n, P<double>(partial), P<double>(gram));
+    check_last("dnc_gram");
+  }, py::arg("stream"), py::arg("rows"), py::arg("ld"), py::arg("W"), py::arg("n"), py::arg("partial"),
+     py::arg("gram"));
 
   // secure aggregation by pairwise masking (csrc/kernels/secagg.hip).  secagg_mask: u[i] = the fixed-point word of
   // x[i] - anchor[i] at frac_bits fraction bits plus the ChaCha20 masks of the W - 1 pairs of `rank` (keys: W x 8

@@ -100,7 +100,6 @@ __global__ __launch_bounds__(kFoldThreads) void krum_finish_kernel(const double*
                                                                    int* record) {
   __shared__ double G[kRobustMaxRanks][kRobustMaxRanks], d[kRobustMaxRanks][kRobustMaxRanks];
   __shared__ double near[kRobustMaxRanks][kRobustMaxRanks], score[kRobustMaxRanks];
-  __shared__ int chosen[kRobustMaxRanks];
   const double sum = fold_partial_tiles(partial, n_partial, P * P);
   const int t = threadIdx.x;
   if (t < P * P) G[t / P][t % P] = sum;
@@ -137,21 +136,7 @@ __global__ __launch_bounds__(kFoldThreads) void krum_finish_kernel(const double*
     score[t] = s;
   }
   __syncthreads();
-  if (t < kRobustMaxRanks) {
-    int before = 0;                                 // clients ahead of t in (score, rank): no score is NaN
-    if (t < W)
-      for (int o = 0; o < W; ++o) before += (score[o] < score[t] || (score[o] == score[t] && o < t)) ? 1 : 0;
-    chosen[t] = (t < W && before < m) ? 1 : 0;
-    stats[t] = score[t];
-    stats[kRobustMaxRanks + t] = chosen[t] ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  if (t < kRobustMaxRanks) {
-    int slot = 0;
-    for (int o = 0; o < t; ++o) slot += chosen[o];
-    if (chosen[t]) record[1 + slot] = t;
-    if (t == 0) record[0] = m;
-  }
+  select_lowest(score, W, m, stats, record);
 }
 
 // The mean of the record's rows, as an operation of flat_map.h.  m and the ranks are the same in every lane: the row
@@ -190,6 +175,10 @@ void launch_gram_pass(hipStream_t st, const float* rows, long ld, int W, long n,
   }
 }
 
+void launch_krum_select(hipStream_t st, const float* rows, long ld, long n, const int* record, float* out) {
+  flat_map(st, n, KrumSelect{rows, ld, record, out});
+}
+
 // rows of 256 doubles in `partial`: one per workgroup of the Gram pass (a function of n only, at most 1024) and one
 // for the record
 int krum_partials(long n) { return n > 0 ? krum_grid(n) + 1 : 0; }
@@ -223,7 +212,7 @@ void launch_krum(hipStream_t st, const float* rows, long ld, int W, long n, int 
   launch_gram_pass(st, rows, ld, W, n, partial);
   hipLaunchKernelGGL(krum_finish_kernel, dim3(1), dim3(kFoldThreads), 0, st, partial, grid, krum_tile(W), W, k, m,
                      nullptr, stats, record);
-  flat_map(st, n, KrumSelect{rows, ld, record, out});
+  launch_krum_select(st, rows, ld, n, record, out);
 }
 
 }  // namespace fedmi

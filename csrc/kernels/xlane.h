@@ -67,6 +67,12 @@ FEDMI_DEV float pin(float v) {
   return v;
 }
 
+// all-reduce sum over a quad: the xor 1, 2 butterfly
+FEDMI_DEV float sum4(float v) {
+  v += dpp<DPP_XOR1>(v);
+  v += dpp<DPP_XOR2>(v);
+  return pin(v);
+}
 // all-reduce sum over aligned groups of 8 lanes: the xor 1, 2, 4 butterfly
 FEDMI_DEV float sum8_steps(float v) {
   v += dpp<DPP_XOR1>(v);

@@ -34,6 +34,7 @@ SOURCES = [
     CSRC / "kernels" / "geomed.hip",
     CSRC / "kernels" / "krum.hip",
     CSRC / "kernels" / "bulyan.hip",
+    CSRC / "kernels" / "dnc.hip",
     CSRC / "kernels" / "secagg.hip",
     CSRC / "kernels" / "compress.hip",
     CSRC / "kernels" / "powersgd.hip",
@@ -53,12 +54,12 @@ SOURCES = [
 ]
 HEADERS = sorted(CSRC.rglob("*.h"))
 
-# per-source flags.  geomed.hip, krum.hip, bulyan.hip, secagg.hip and powersgd.hip name every fp32 rounding of their rules (__fadd_rn, __fmaf_rn,
+# per-source flags.  geomed.hip, krum.hip, bulyan.hip, dnc.hip, secagg.hip and powersgd.hip name every fp32 rounding of their rules (__fadd_rn, __fmaf_rn,
 # __fsub_rn, __fmul_rn): they are built without packed fp32 instructions, so each of them is the scalar instruction the
 # rule means.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"geomed.hip": _NO_PACKED_FP32, "krum.hip": _NO_PACKED_FP32, "bulyan.hip": _NO_PACKED_FP32,
-               "secagg.hip": _NO_PACKED_FP32, "powersgd.hip": _NO_PACKED_FP32}
+               "dnc.hip": _NO_PACKED_FP32, "secagg.hip": _NO_PACKED_FP32, "powersgd.hip": _NO_PACKED_FP32}
 
 
 # build variants: the module name carries the variant (csrc/bindings.cpp FEDMI_MODULE); an A/B build adds

@@ -30,7 +30,8 @@ client still computes the same bits from the same rows.
 The float state is gathered as for the other rules (:class:`fedmi.parallel.robust.GatheredAgg`) and reduced by ``krum``
 (csrc/kernels/krum.hip: the Gram as fp64 MFMA tiles, a one-workgroup finish, a copy of the selected rows; three
 launches, no host sync) on a GPU or by :func:`krum_torch` on the CPU.  Bulyan builds on the same Gram pass
-(:mod:`fedmi.parallel.bulyan`).  Not built: a fused peer kernel, client subsampling, a centred Gram.
+(:mod:`fedmi.parallel.bulyan`).  Not built: a fused peer kernel, client subsampling, the distances from a centred Gram
+(:mod:`fedmi.parallel.dnc` has the centred pass).
 """
 from __future__ import annotations
 

@@ -94,7 +94,7 @@ def robust_reduce_torch(rows: torch.Tensor, b_eff: int) -> Tuple[torch.Tensor, t
 class GatheredAgg(ReplicatedState):
     """Base of the rules that replace FedAvg's mean by a function of all clients' gathered float states
     (:class:`RobustAgg`, :class:`fedmi.parallel.geomed.GeoMedAgg`,
-    :class:`fedmi.parallel.krum.KrumAgg`, :class:`fedmi.parallel.bulyan.BulyanAgg`).  Stateless across rounds: nothing is rolled back or
+    :class:`fedmi.parallel.krum.KrumAgg`, :class:`fedmi.parallel.bulyan.BulyanAgg`, :class:`fedmi.parallel.dnc.DncAgg`).  Stateless across rounds: nothing is rolled back or
     handed over; the class exists so that ``resync`` compares the settings across clients and raises on the one that
     differs.  Holds the ``[W, ld]`` gather buffer, the kernels' partials and the host mirror of ``stats``, the device
     statistics of the last call.  A subclass supplies :meth:`_reduce` and :meth:`_decode`."""
@@ -250,13 +250,15 @@ class RobustAgg(GatheredAgg):
 def add_robust_flags(ap) -> None:
     """``--robust``, ``--robust-trim``, ``--robust-iters``, ``--robust-nu`` and ``--robust-byz`` (fedmi.cli.client,
     tools/fedavg_sim.py)."""
-    ap.add_argument("--robust", default="none", choices=["none", *KINDS, "geomed", "krum", "multikrum", "bulyan"],
+    ap.add_argument("--robust", default="none", choices=["none", *KINDS, "geomed", "krum", "multikrum", "bulyan", "dnc"],
                     help="Byzantine-robust aggregation (fedmi.parallel.robust): the coordinate-wise median or trimmed "
                          "mean of the clients' models replaces the plain mean; every client must pass the same settings."
                          "  geomed (fedmi.parallel.geomed): the geometric median of the clients' whole models.  krum / "
                          "multikrum (fedmi.parallel.krum): the client nearest to its peers, or the mean of the nearest.  "
                          "bulyan (fedmi.parallel.bulyan): Krum, iterated, selects the clients and every coordinate is "
-                         "the mean of their values closest to the median")
+                         "the mean of their values closest to the median.  dnc (fedmi.parallel.dnc): the clients that "
+                         "stand out along the top principal direction of the centred models are dropped, the rest "
+                         "averaged")
     ap.add_argument("--robust-trim", type=int, default=1, metavar="B",
                     help="trimmed: cut the B smallest and the B largest values of every coordinate (at most "
                          "(clients - 1) // 2 are cut: a shrinking federation degrades towards the median)")
@@ -267,7 +269,8 @@ def add_robust_flags(ap) -> None:
     ap.add_argument("--robust-byz", type=int, default=1, metavar="F",
                     help="krum / multikrum: the number of arbitrary clients to withstand (at most (clients - 3) // 2 "
                          "count: a shrinking federation degrades and does not fail).  bulyan: at most (clients - 3) // 4 "
-                         "count, and twice as many clients are left out and values cut per coordinate")
+                         "count, and twice as many clients are left out and values cut per coordinate.  dnc: the number "
+                         "of clients dropped, at most (clients - 1) // 2")
 
 
 def compression_on(a) -> bool:
@@ -305,7 +308,7 @@ def check_robust_flags(a, error) -> None:
 def make_robust(kind: Optional[str], trainer=None, trim: int = 1, iters: int = 8, nu: float = 1e-6, byz: int = 1):
     """None for ``none`` (nothing new is launched); a :class:`fedmi.parallel.geomed.GeoMedAgg` for ``geomed``, a
     :class:`fedmi.parallel.krum.KrumAgg` for ``krum`` and ``multikrum``, a :class:`fedmi.parallel.bulyan.BulyanAgg`
-    for ``bulyan``."""
+    for ``bulyan``, a :class:`fedmi.parallel.dnc.DncAgg` for ``dnc``."""
     if kind in (None, "", "none"):
         return None
     if kind in ("krum", "multikrum"):
@@ -316,6 +319,10 @@ def make_robust(kind: Optional[str], trainer=None, trim: int = 1, iters: int = 8
         from .bulyan import BulyanAgg, BulyanConfig
 
         return BulyanAgg(trainer, BulyanConfig(kind, byz))
+    if kind == "dnc":
+        from .dnc import DncAgg, DncConfig
+
+        return DncAgg(trainer, DncConfig(kind, byz))
     if kind == "geomed":
         from .geomed import GeoMedAgg, GeoMedConfig
 
